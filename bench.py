@@ -23,6 +23,7 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -119,6 +120,28 @@ def shard_captions(lengths, tokens, c0, c1, dev):
     tok_off = np.concatenate([[0], np.cumsum(lens_sorted)[:-1]]) if len(order) else np.zeros(0, np.int64)
     return (torch.from_numpy(packed.astype(np.int64)).to(dev), torch.from_numpy(tok_off.astype(np.int64)).to(dev),
             [int(x) for x in lens_sorted], order)
+
+
+RANK_NAMES = ("i2t_rank", "i2t_top1", "t2i_rank", "t2i_top1")
+DUMP_SCORE_ROWS = 256
+DUMP_SCORE_BYTES = 48 << 20
+
+
+def dump_outputs(d, S, ranks, row0):
+    """--dump-outputs: what the last timed step handed its caller.  The four rank vectors whole (float64: exact for these
+    integers); of the score matrix (this rank's row block, ~0.5 GB at 5k x 25k) the full rows of a fixed, seeded sample of rows,
+    with their global row indices.  At most DUMP_SCORE_BYTES + the rank vectors on disk."""
+    os.makedirs(d, exist_ok=True)
+    for name, r in zip(RANK_NAMES, ranks):
+        np.save(os.path.join(d, name + ".npy"), np.asarray(r).astype(np.float64))
+    if S is None:          # --stream-scores: the timed step kept no matrix
+        return
+    n_rows, n_cols = S.shape
+    k = min(n_rows, DUMP_SCORE_ROWS, max(1, DUMP_SCORE_BYTES // (4 * max(1, n_cols))))
+    rows = np.sort(np.random.RandomState(0).choice(n_rows, size=k, replace=False))
+    sample = S.index_select(0, torch.from_numpy(rows).to(S.device)).float().cpu().numpy()
+    np.save(os.path.join(d, "score_rows.npy"), sample)
+    np.save(os.path.join(d, "score_row_index.npy"), (rows + row0).astype(np.float64))
 
 
 def host_info():
@@ -343,6 +366,10 @@ BERT_BASE = dict(vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_at
                  hidden_act="gelu", initializer_range=0.02)
 
 
+# the seeded BERT-base files bert_files() writes once and reuses: per user, so that a copy another account left is never in the way
+BERT_DIR = os.path.join(tempfile.gettempdir(), "itr_bench_bert_%d" % os.getuid())
+
+
 def bert_files(tmp):
     """bert_config.json + a seeded random pytorch_model.bin + SAEM's trans_cfg.json (pretrained weights are external
     to the reference and there is no network: SURVEY 8c)."""
@@ -405,7 +432,7 @@ def main_pooled(args, wl, world, rank, dev, use_dist):
         cfg = C.build_config(['with', 'VSRN', 'data_name=%s_precomp' % ("coco" if wl["n_img"] == 5000 else "f30k")])
         cfg.update(vocab_size=wl["vocab"])
     else:
-        cfg_file, ckpt, trans = bert_files(os.path.join("/tmp", "itr_bench_bert"))
+        cfg_file, ckpt, trans = bert_files(BERT_DIR)
         cfg = C.build_config(['with', kind, 'data_name=coco_precomp'])
         cfg.update(bert_config_file=cfg_file, init_checkpoint=ckpt, trans_cfg=trans, vocab_size=30522)
     torch.manual_seed(0)       # (bert_files() draws random numbers only when it has to create the checkpoint: seed AFTER it)
@@ -504,6 +531,8 @@ def main_pooled(args, wl, world, rank, dev, use_dist):
         streamed_equal = all(np.array_equal(np.asarray(a), np.asarray(b)) for a, b in zip(ranks, ranks_kept))
     if rank != 0:
         return None
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, None if streamed else S, ranks, i0)
     from itr_amd import ops as _ops
     ms_per_step = 1e3 * dt / args.steps
     # SURVEY 8d algorithmic flop of the step on this rank
@@ -988,7 +1017,12 @@ def main():
     ap.add_argument("--from-files", default=None, metavar="DIR",
                     help="time the file -> rank path on a precomp dataset directory written by tools/make_synth_precomp.py (SCAN t2i): "
                          "memory-mapped .npy -> pinned -> HBM, tokenise, encode, score, rank; reported next to the resident-input number")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0): the four rank vectors "
+                         "(float64) and a fixed, seeded sample of score-matrix rows (float32), to compare two builds output for output")
     args = ap.parse_args()
+    if args.dump_outputs and (args.launch_check or args.from_files):
+        ap.error("--dump-outputs applies to the resident-input workloads (not --launch-check / --from-files)")
     if args.cpu_threads:
         global CPU_THREADS
         CPU_THREADS = [int(x) for x in args.cpu_threads.split(",")]
@@ -1160,7 +1194,8 @@ def other_configs(args, world, rank, dev, use_dist, backend, line):
                 o, err = other_config_in_child(name, k, w, 240)
                 ok = int(o is not None)
             else:
-                a2 = argparse.Namespace(**dict(vars(args), workload=name, steps=k, warmup=w, no_cpu_baseline=True, no_variants=True))
+                a2 = argparse.Namespace(**dict(vars(args), workload=name, steps=k, warmup=w, no_cpu_baseline=True, no_variants=True,
+                                               dump_outputs=None))
                 try:
                     o = run_workload(a2, world, rank, dev, use_dist, backend, primary=False)
                 except Exception as e:      # noqa: BLE001
@@ -1274,6 +1309,8 @@ def main_words(args, world, rank, dev, use_dist, backend, primary=True):
     per_rank = gather_floats([min(step_ms), max(step_ms), float(np.mean(step_ms)), float(np.mean(scan_ms)), wait_ms], dev, backend, use_dist)
 
     if rank == 0:
+        if primary and getattr(args, "dump_outputs", None):
+            dump_outputs(args.dump_outputs, S, ranks, i0)
         ms_per_step = 1e3 * dt / args.steps
         pairs = float(n_img) * n_cap
         n_words = int(lengths.sum())

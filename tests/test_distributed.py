@@ -292,3 +292,31 @@ def test_bench_parent_makes_no_gpu_call_before_launching():
     lr = [n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == "launch_ranks"][0]
     body = "\n".join(src.splitlines()[lr.body[1].lineno - 1:lr.end_lineno])      # (past the docstring)
     assert "torch.cuda" not in body and "os.exec" not in body and "execv" not in body
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """--dump-outputs: the four rank vectors whole (float64, exact), a seeded sample of full score rows (float32) with their global
+    row indices, the same sample every time, and at most 64 MB in all."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    n_rows, n_cols, row0 = 1000, 25000, 40
+    S = torch.randn(n_rows, n_cols, generator=torch.Generator().manual_seed(0))
+    rng = np.random.RandomState(1)
+    ranks = tuple(rng.randint(0, 5000, size=n).astype(np.int64) for n in (n_rows, n_rows, n_cols, n_cols))
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        bench.dump_outputs(d, S, ranks, row0)
+    files = sorted(os.listdir(dirs[0]))
+    assert files == sorted([n + ".npy" for n in bench.RANK_NAMES] + ["score_rows.npy", "score_row_index.npy"])
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in files) <= 64 << 20
+    for name, r in zip(bench.RANK_NAMES, ranks):
+        a = np.load(os.path.join(dirs[0], name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, r)
+    rows, idx = np.load(os.path.join(dirs[0], "score_rows.npy")), np.load(os.path.join(dirs[0], "score_row_index.npy"))
+    assert rows.dtype == np.float32 and rows.shape == (bench.DUMP_SCORE_ROWS, n_cols) and idx.dtype == np.float64
+    assert np.array_equal(rows, S.numpy()[idx.astype(np.int64) - row0])
+    for f in files:
+        assert np.array_equal(np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f)))
+    bench.dump_outputs(str(tmp_path / "c"), None, ranks, row0)          # --stream-scores: no matrix was kept
+    assert sorted(os.listdir(str(tmp_path / "c"))) == sorted(n + ".npy" for n in bench.RANK_NAMES)

@@ -162,7 +162,7 @@ def test_pooled_bert_models_full_size(dev, kind):
     from itr_amd import config as C, evalpipe
     from itr_amd.modalmodule import get_model
     n_img, n_cap = 5000, 25000
-    cfg_file, ckpt, trans = bench.bert_files(os.path.join("/tmp", "itr_bench_bert"))
+    cfg_file, ckpt, trans = bench.bert_files(bench.BERT_DIR)
     cfg = C.build_config(['with', kind, 'data_name=coco_precomp'])
     cfg.update(bert_config_file=cfg_file, init_checkpoint=ckpt, trans_cfg=trans, vocab_size=30522)
     torch.manual_seed(0)

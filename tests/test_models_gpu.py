@@ -235,6 +235,10 @@ def test_virtual_split_runs_the_multi_rank_branch_on_one_gpu(workload, split):
         assert virt["recall"] == plain["recall"]
 
 
+# ranks of one test that may share a single GPU: each holds its own context and workspaces, and the test process holds one too
+RANKS_SHARING_ONE_GPU = 4
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload,world", [("scan_t2i_f30k1k", 2), ("scan_t2i_f30k1k", 3), ("sgraf_saf_f30k1k", 2), ("sgraf_sgr_f30k1k", 3),
                                             ("vsepp_f30k1k", 2), ("vsrn_f30k1k", 2), ("camera_f30k1k", 2),
@@ -244,7 +248,12 @@ def test_sharded_eval_equals_single_process_on_one_gpu(workload, world):
     ragged rank gather) with real kernels: `world` ranks share this box's one GPU through the gloo backend (RCCL refuses
     two ranks per device) and must reproduce the single-process rank vectors exactly.  The two world-8 cases are the REAL
     partition of BASELINE configs[2] / [4]: 5 000 images in row blocks of 628 / ... / 604, 25 000 captions in token-balanced
-    ranges (VERDICT r2 #2b)."""
+    ranges (VERDICT r2 #2b).  Up to RANKS_SHARING_ONE_GPU ranks share one device; a larger world needs a GPU per rank (with gloo,
+    rank r runs on device r % device_count)."""
+    import torch
+    n_dev = torch.cuda.device_count()
+    if world > RANKS_SHARING_ONE_GPU and n_dev < world:
+        pytest.skip("needs %d GPUs, found %d" % (world, n_dev))
     single = _bench_line(_base_args(workload))
     # (world 8 on ONE GPU: eight SGRAF workspaces side by side -- the smaller image block of rounds 1-3; scores do not depend on it)
     multi = _bench_line(["--gpus", str(world)] + _base_args(workload), env=dict(ITR_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", ITR_SGRAF_IB="16"),
@@ -380,3 +389,31 @@ def test_from_files_path_single_and_two_ranks(tmp_path):
                  "--master-port", "29577", base[0], "--gpus", "2"] + base[1:], env)
     assert multi["n_gpus"] == 2 and multi["ranks_identical_to_resident"]
     assert multi["rank_checksum"] == single["rank_checksum"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["scan_t2i_f30k1k", "vsepp_f30k1k"])
+def test_bench_dump_outputs_are_the_last_timed_step(workload, tmp_path):
+    """bench.py --dump-outputs DIR: --steps timed steps ran, and DIR holds the rank vectors of the line (same checksums, float64)
+    and float32 score rows that rank like the line's i2t vector on the sampled rows; a second run writes the same ranks."""
+    import numpy as np
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        out = _bench_line(["--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-variants", "--no-other-configs",
+                           "--dump-outputs", d])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        dumps.append({n: np.load(os.path.join(d, n + ".npy")) for n in bench.RANK_NAMES + ("score_rows", "score_row_index")})
+    a, b = dumps
+    ranks = [a[n] for n in bench.RANK_NAMES]
+    assert all(r.dtype == np.float64 for r in ranks)
+    assert [int((r.astype(np.int64) * (np.arange(len(r)) % 9973 + 1)).sum()) for r in ranks] == out["rank_checksum"]
+    assert a["score_rows"].dtype == np.float32 and a["score_rows"].shape[1] == 5 * out["config"]["n_img"]
+    rows = a["score_row_index"].astype(np.int64)
+    top1 = a["score_rows"].shape[1] - 1 - np.argmax(a["score_rows"][:, ::-1], axis=1)
+    assert np.array_equal(top1, a["i2t_top1"][rows].astype(np.int64))
+    for n in bench.RANK_NAMES + ("score_row_index",):
+        assert np.array_equal(a[n], b[n]), n

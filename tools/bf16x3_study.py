@@ -21,7 +21,7 @@ n_cap = 5 * n_img
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 if kind in ("SAEM", "CAMERA"):
-    cfg_file, ckpt, trans = bench.bert_files(os.path.join("/tmp", "itr_bench_bert"))
+    cfg_file, ckpt, trans = bench.bert_files(bench.BERT_DIR)
     cfg = C.build_config(['with', kind, 'data_name=coco_precomp'])
     cfg.update(bert_config_file=cfg_file, init_checkpoint=ckpt, trans_cfg=trans, vocab_size=30522)
     model = get_model(cfg)

@@ -5,7 +5,7 @@ from itr_amd import config as C, ops
 from itr_amd.modalmodule import get_model
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
-cfg_file, ckpt, trans = bench.bert_files(os.path.join("/tmp", "itr_bench_bert"))
+cfg_file, ckpt, trans = bench.bert_files(bench.BERT_DIR)
 cfg = C.build_config(['with', 'CAMERA', 'data_name=coco_precomp'])
 cfg.update(bert_config_file=cfg_file, init_checkpoint=ckpt, trans_cfg=trans, vocab_size=30522)
 model = get_model(cfg); model.val_start()

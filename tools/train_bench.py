@@ -126,7 +126,7 @@ def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=N
     cfg['img_dim'] = 2048        # precomp region features
     if model_name in ('SAEM', 'CAMERA'):
         import bench
-        cfg_file, ckpt, trans = bench.bert_files(os.path.join("/tmp", "itr_bench_bert"))
+        cfg_file, ckpt, trans = bench.bert_files(bench.BERT_DIR)
         cfg.update(bert_config_file=cfg_file, init_checkpoint=ckpt, trans_cfg=trans, vocab_size=30522, batch_size=batch)
     torch.manual_seed(0)
     model = get_model(cfg)
