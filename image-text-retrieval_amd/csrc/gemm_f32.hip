@@ -17,7 +17,7 @@
 // `group` > 1 fuses a max over `group` consecutive rows into the epilogue
 // (MultiViewMatching, Fusionmodule.py:674-692: S[i,c] = max_v img[i,v,:] . cap[c,:]); the M tile
 // then covers (128 / group) * group rows so no group straddles two tiles.
-#include "itr_common.h"
+#include "itr_internal.h"
 
 namespace itr {
 
@@ -438,19 +438,18 @@ int gemm_nt_splitk_fast(const float *A, int64_t lda, const float *B, int64_t ldb
 
 // Slices only: scratch[s][m][n] (s < *n_slices) holds the raw partial products; the CONSUMER adds them (in slice order) --
 // the GRU gate kernels do, which saves one launch and one pass per time step.
-bool gemm_skinny_ok(const float *A, int64_t lda, const float *B, int64_t ldb, int64_t M, int64_t N, int64_t K);      // gemm_skinny.hip
-int gemm_skinny_partials(const float *A, int64_t lda, const float *B, int64_t ldb, int64_t M, int64_t N, int64_t K, int max_slices, float *part,
-                         int *n_slices, hipStream_t st);
 int gemm_nt_splitk_partials(const float *A, int64_t lda, const float *B, int64_t ldb, int64_t M, int64_t N, int64_t K, int splits, float *scratch,
-                            int *n_slices, hipStream_t st) {
+                            size_t scratch_bytes, int *n_slices, hipStream_t st) {
     *n_slices = 0;
     if (M == 0 || N == 0) return ITR_OK;
+    const size_t fit = scratch_bytes / gemm_splitk_scratch_bytes(M, N, 1);      // whole M x N slices
     // M <= 128 rows (a training batch's recurrence): 16-column strips over all rows instead of one 128-row tile per 128 columns
-    // (gemm_skinny.hip); the caller's scratch holds 16 slices of M x N, the consumer adds whatever number of slices comes back
-    if (splits > 1 && !ITR_EXP_ENV("ITR_GEMM_NO_SKINNY") && gemm_skinny_ok(A, lda, B, ldb, M, N, K))
-        return gemm_skinny_partials(A, lda, B, ldb, M, N, K, 16, scratch, n_slices, st);
+    // (gemm_skinny.hip), up to 16 slices of M x N as the scratch holds; the consumer adds whatever number of slices comes back
+    if (splits > 1 && fit >= 1 && !ITR_EXP_ENV("ITR_GEMM_NO_SKINNY") && gemm_skinny_ok(A, lda, B, ldb, M, N, K))
+        return gemm_skinny_partials(A, lda, B, ldb, M, N, K, fit < 16 ? (int)fit : 16, scratch, n_slices, st);
     const int64_t ksplit = ceil_div(ceil_div(K, (int64_t)(splits > 1 ? splits : 1)), (int64_t)BK) * BK;
     const int ns = (int)ceil_div(K, ksplit);
+    ITR_REQUIRE((size_t)ns <= fit, "gemm_nt_splitk_partials: %d slices do not fit %zu bytes of scratch", ns, scratch_bytes);
     GemmArgs g{A, B, nullptr, scratch, lda, ldb, N, M, N, K, 0, 1, BM, nullptr, nullptr, 0, 0, ksplit, scratch};
     const int64_t nblk = ceil_div(M, BM) * ceil_div(N, BN);
     const bool aligned = (lda % 4 == 0) && (ldb % 4 == 0) && (K % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0) &&
@@ -464,17 +463,12 @@ int gemm_nt_splitk_partials(const float *A, int64_t lda, const float *B, int64_t
     return ITR_OK;
 }
 
-bool gemm_nt_stream(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int64_t M,
-                    int64_t N, int64_t K, int act, hipStream_t st, int *rc, int algo);      // gemm_stream.hip
-
 static int gemm_nt_algo(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C,
                         int64_t ldc, int64_t M, int64_t N, int64_t K, int act, hipStream_t st, int algo);
 int gemm_nt(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C,
             int64_t ldc, int64_t M, int64_t N, int64_t K, int act, hipStream_t st) {
     return gemm_nt_algo(A, lda, B, ldb, bias, C, ldc, M, N, K, act, st, 0);
 }
-int gemm_skinny_direct(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int64_t M, int64_t N, int64_t K,
-                       int act, hipStream_t st);      // gemm_skinny.hip
 static int gemm_nt_algo(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C,
                         int64_t ldc, int64_t M, int64_t N, int64_t K, int act, hipStream_t st, int algo) {
     // algo 4 (the training tape's request for a batch of <= 128 rows: a decoder step, a per-caption vector layer): 16-column strips over

@@ -9,7 +9,7 @@
 // banks).  Grid = (N / 16) x slices, slices chosen for ~1.5 workgroups per CU; the slices' partial products are written one after the other
 // ([slice][m][n]) and summed -- in slice order, with the bias -- by the GRU gate kernels that consume them, exactly as the tile kernel's
 // slices were.  Row tiles past the active prefix are skipped by whole waves.
-#include "itr_common.h"
+#include "itr_internal.h"
 
 namespace itr {
 

@@ -12,7 +12,7 @@
 // The body is one generated asm statement (gemm_stream_asm.inc, tools/gen_gemm_stream.py) with hand-allocated registers:
 // see scan_mainloop.inc for why the loops that hide loads from hipcc are not written in C++ any more.
 // Preconditions (checked by the host wrapper): M % 128 == 0, N % 128 == 0, K % 64 == 0, K >= 128, 16-byte aligned rows.
-#include "itr_common.h"
+#include "itr_internal.h"
 #include <mutex>
 
 namespace itr {

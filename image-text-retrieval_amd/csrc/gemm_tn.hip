@@ -11,7 +11,7 @@
 //   * blockIdx.y owns a slice of the rows and writes a raw partial product; gemm_tn_reduce_kernel adds the slices in slice order
 //     (deterministic) and stores or accumulates.  The slice count is chosen so that tiles x slices ~ 4 workgroups per CU.
 // Exact fp32 (the MFMA is an fmaf chain); only the order of the row sum differs from the NT form.
-#include "itr_common.h"
+#include "itr_internal.h"
 
 namespace itr {
 

@@ -16,22 +16,10 @@
 //     dW_hh = dgh^T H_prev    db_hh = colsum(dgh)    dW_ih = dgi^T X    db_ih = colsum(dgi)    dX (+)= dgi W_ih
 // and dE[token] += dX (atomic scatter; the only non-deterministic summation order of the step).
 #include <stdlib.h>
-#include "itr_common.h"
+#include "itr_internal.h"
 #include "side_stream.h"
 
 namespace itr {
-
-int gemm_nt(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc,
-            int64_t M, int64_t N, int64_t K, int act, hipStream_t st);
-int gemm_nt_acc(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc,
-                int64_t M, int64_t N, int64_t K, int act, hipStream_t st);
-// skinny GEMMs of the recurrence (M = batch): split-K with a deterministic reduction (gemm_f32.hip)
-int gemm_splitk_choice(int64_t M, int64_t N, int64_t K);
-size_t gemm_splitk_scratch_bytes(int64_t M, int64_t N, int splits);
-int gemm_nt_splitk(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int64_t M, int64_t N,
-                   int64_t K, int act, int accumulate, int splits, float *scratch, hipStream_t st);
-int gemm_nt_splitk_partials(const float *A, int64_t lda, const float *B, int64_t ldb, int64_t M, int64_t N, int64_t K, int splits, float *scratch,
-                            int *n_slices, hipStream_t st);
 
 __device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + expf(-v)); }
 
@@ -135,8 +123,6 @@ static int transpose(const float *in, float *out, int64_t rows, int64_t cols, in
     return ITR_OK;
 }
 
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static int check_lengths(const int32_t *len_host, int64_t B, int64_t n_tok, const char *who) {
     int64_t total = 0;
     for (int64_t b = 0; b < B; ++b) {
@@ -177,45 +163,41 @@ struct GruTrainWs {
         float *gi, *gh, *h;           // forward: gate pre-activations of all tokens; [B, 3D] recurrence product; [B, D] state
         float *hprev, *carry, *dgh_step, *whhT, *wihT, *skbuf;
         void *tn;                     // gemm_tn partials of the two weight gradients
-        size_t tn_bytes;
     } d[2];                           // backward: gi / gh double as dgi / dgh
+    size_t sk_bytes, tn_bytes, bytes; // skbuf and tn of each direction; the whole workspace
 };
-size_t gemm_tn_workspace_bytes(int64_t R, int P, int Q);
-int gemm_tn(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc, int64_t R, int P, int Q, int accumulate,
-            float *colsum_a, void *workspace, size_t workspace_bytes, hipStream_t st);
-
-static size_t gru_train_ws_carve(void *base, int64_t n_tok, int64_t B, int E, int D, GruTrainWs *w) {
+static GruTrainWs gru_train_ws(void *base, int64_t n_tok, int64_t B, int E, int D) {
     const size_t nt = (size_t)n_tok, d3 = (size_t)3 * D;
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t bytes) { char *q = p; p += al256(bytes); return q; };
+    WsCarver c(base);
     GruTrainWs t;
-    t.x = (float *)take(nt * E * 4);
-    t.dx = (float *)take(nt * E * 4);
-    t.out_rev = (float *)take(nt * D * 4);
-    t.bad = (int *)take(512);
-    const size_t tnb = gemm_tn_workspace_bytes(n_tok, 3 * D, D > E ? D : E);
+    t.x = c.take<float>(nt * E * 4);
+    t.dx = c.take<float>(nt * E * 4);
+    t.out_rev = c.take<float>(nt * D * 4);
+    t.bad = c.take<int>(512);
+    // the backward runs gemm_tn with Q = D and with Q = E, and its partials do not grow monotonically with Q
+    const size_t tn_d = gemm_tn_workspace_bytes(n_tok, 3 * D, D), tn_e = gemm_tn_workspace_bytes(n_tok, 3 * D, E);
+    t.tn_bytes = tn_d > tn_e ? tn_d : tn_e, t.sk_bytes = gemm_splitk_scratch_bytes(B, 3 * D, 16);
     for (int k = 0; k < 2; ++k) {
-        t.d[k].gi = (float *)take(nt * d3 * 4);
-        t.d[k].gh = (float *)take(nt * d3 * 4);
-        t.d[k].h = (float *)take((size_t)B * D * 4);
-        t.d[k].hprev = (float *)take(nt * D * 4);
-        t.d[k].carry = (float *)take((size_t)B * D * 4);
-        t.d[k].dgh_step = (float *)take((size_t)B * d3 * 4);
-        t.d[k].whhT = (float *)take(d3 * D * 4);
-        t.d[k].wihT = (float *)take(d3 * E * 4);
-        t.d[k].skbuf = (float *)take(gemm_splitk_scratch_bytes(B, 3 * D, 16));
-        t.d[k].tn = take(tnb);
-        t.d[k].tn_bytes = tnb;
+        t.d[k].gi = c.take<float>(nt * d3 * 4);
+        t.d[k].gh = c.take<float>(nt * d3 * 4);
+        t.d[k].h = c.take<float>((size_t)B * D * 4);
+        t.d[k].hprev = c.take<float>(nt * D * 4);
+        t.d[k].carry = c.take<float>((size_t)B * D * 4);
+        t.d[k].dgh_step = c.take<float>((size_t)B * d3 * 4);
+        t.d[k].whhT = c.take<float>(d3 * D * 4);
+        t.d[k].wihT = c.take<float>(d3 * E * 4);
+        t.d[k].skbuf = c.take<float>(t.sk_bytes);
+        t.d[k].tn = c.take(t.tn_bytes);
     }
-    if (w) *w = t;
-    return (size_t)(p - static_cast<char *>(base));
+    t.bytes = c.bytes;
+    return t;
 }
 
 }  // namespace itr
 using namespace itr;
 
 extern "C" size_t itr_gru_train_workspace_bytes(int64_t n_tok, int64_t B, int E, int D) {
-    return gru_train_ws_carve(nullptr, n_tok > 0 ? n_tok : 1, B > 0 ? B : 1, E, D, nullptr);
+    return gru_train_ws(nullptr, n_tok > 0 ? n_tok : 1, B > 0 ? B : 1, E, D).bytes;
 }
 
 __global__ __launch_bounds__(256) void gru_avg_kernel(float *__restrict__ out, const float *__restrict__ other, int64_t n) {
@@ -238,8 +220,7 @@ extern "C" int itr_gru_fwd_train(const int64_t *tokens, const int64_t *tok_off, 
     int rc = check_lengths(len_host, B, n_tok, "itr_gru_fwd_train");
     if (rc != ITR_OK) return rc;
     hipStream_t st = as_stream(stream);
-    GruTrainWs w;
-    gru_train_ws_carve(workspace, n_tok, B, E, D, &w);
+    GruTrainWs w = gru_train_ws(workspace, n_tok, B, E, D);
     const int splits_h = gemm_splitk_choice(B, 3 * D, D);
     const bool fuse = ITR_EXP_ENV("ITR_GRU_REDUCE_KERNEL") == nullptr;   // tools/ A/B switch: separate reduction kernel
     const int Lmax = len_host[0];
@@ -264,7 +245,7 @@ extern "C" int itr_gru_fwd_train(const int64_t *tokens, const int64_t *tok_off, 
         for (int t = 0; t < Lmax; ++t) {
             while (n_act > 0 && len_host[n_act - 1] <= t) --n_act;
             int ns = 0;
-            if (splits_h > 1 && fuse) rc2 = gemm_nt_splitk_partials(d.h, D, wh, D, n_act, 3 * D, D, splits_h, d.skbuf, &ns, sd);
+            if (splits_h > 1 && fuse) rc2 = gemm_nt_splitk_partials(d.h, D, wh, D, n_act, 3 * D, D, splits_h, d.skbuf, w.sk_bytes, &ns, sd);
             else rc2 = gemm_nt_splitk(d.h, D, wh, D, bh, d.gh, 3 * D, n_act, 3 * D, D, 0, 0, splits_h, d.skbuf, sd);
             if (rc2 != ITR_OK) return rc2;
             // the reverse direction writes its own output plane; the average with the forward direction follows the join
@@ -301,8 +282,7 @@ extern "C" int itr_gru_bwd(const int64_t *tokens, const int64_t *tok_off, const 
     int rc = check_lengths(len_host, B, n_tok, "itr_gru_bwd");
     if (rc != ITR_OK) return rc;
     hipStream_t st = as_stream(stream);
-    GruTrainWs w;
-    gru_train_ws_carve(workspace, n_tok, B, E, D, &w);
+    GruTrainWs w = gru_train_ws(workspace, n_tok, B, E, D);
     const int splits_c = gemm_splitk_choice(B, D, 3 * D);
     const bool fuse = ITR_EXP_ENV("ITR_GRU_REDUCE_KERNEL") == nullptr;
     const int Lmax = len_host[0];
@@ -339,7 +319,7 @@ extern "C" int itr_gru_bwd(const int64_t *tokens, const int64_t *tok_off, const 
             ns_pending = 0;
             if (t > 0) {
                 if (splits_c > 1 && fuse) {   // slices of dgh W_hh stay in scratch: the next gate kernel adds them to carry
-                    GB_TRY(gemm_nt_splitk_partials(d.dgh_step, 3 * D, d.whhT, 3 * D, n_act, D, 3 * D, splits_c, d.skbuf, &ns_pending, sd));
+                    GB_TRY(gemm_nt_splitk_partials(d.dgh_step, 3 * D, d.whhT, 3 * D, n_act, D, 3 * D, splits_c, d.skbuf, w.sk_bytes, &ns_pending, sd));
                     prev_n = n_act;
                 } else {
                     GB_TRY(gemm_nt_splitk(d.dgh_step, 3 * D, d.whhT, 3 * D, nullptr, d.carry, D, n_act, D, 3 * D, 0, 1, splits_c, d.skbuf, sd));
@@ -347,8 +327,8 @@ extern "C" int itr_gru_bwd(const int64_t *tokens, const int64_t *tok_off, const 
             }
         }
         // weight gradients over all tokens: dW = dg^T A on the split-row TN GEMM, the bias gradient (column sums of dg) from the same pass
-        GB_TRY(gemm_tn(dgh, 3 * D, d.hprev, D, dwh, D, n_tok, 3 * D, D, 0, dbh, d.tn, d.tn_bytes, sd));
-        GB_TRY(gemm_tn(dgi, 3 * D, w.x, E, dwi, E, n_tok, 3 * D, E, 0, dbi, d.tn, d.tn_bytes, sd));
+        GB_TRY(gemm_tn(dgh, 3 * D, d.hprev, D, dwh, D, n_tok, 3 * D, D, 0, dbh, d.tn, w.tn_bytes, sd));
+        GB_TRY(gemm_tn(dgi, 3 * D, w.x, E, dwi, E, n_tok, 3 * D, E, 0, dbi, d.tn, w.tn_bytes, sd));
         return ITR_OK;
     };
     rc = ITR_OK;

@@ -1,7 +1,7 @@
 // Row normalisation (itr/modalmodule/utils.py:4-15): y = x / (norm(x) + eps), eps AFTER the
 // sqrt -- this is not F.normalize, and parity depends on it.  HBM-bound: one wave per row,
 // float4 loads, wave-shuffle reduction; rows up to 4096 floats stay in registers (one read).
-#include "itr_common.h"
+#include "itr_internal.h"
 
 namespace itr {
 

@@ -14,7 +14,7 @@
 // float64 matrices (ensemble averages) keep one pass per direction.
 // S may be a row block of the global matrix (multi-GPU row sharding): row0 is the global index
 // of its first row, and s_gt[] carries the GT score of every caption (gathered over ranks).
-#include "itr_common.h"
+#include "itr_internal.h"
 #include <mutex>
 
 namespace itr {
@@ -510,12 +510,18 @@ extern "C" int itr_rank_gather_gt(const float *S, int64_t ldS, int64_t row0, int
     return ITR_OK;
 }
 
-static inline size_t rank_al(size_t v) { return (v + 255) & ~(size_t)255; }
-extern "C" size_t itr_rank_workspace_bytes(int64_t n_rows_local, int64_t Nc) {
-    const size_t nr = (size_t)(n_rows_local > 0 ? n_rows_local : 0), nc = (size_t)(Nc > 0 ? Nc : 0);
-    // per local row: its best GT key + its running top-1 key; per column: the GT score when the call gathers it itself
-    return rank_al(nr * 16) + rank_al(nc * 4) + 256;
+// per local row: its best GT key + its running top-1 key; per column: the GT score when the call gathers it itself
+struct RankWs { unsigned long long *row_keys; float *gt_own; size_t bytes; };
+static RankWs rank_ws(void *base, int64_t n_rows_local, int64_t Nc) {
+    itr::WsCarver c(base);
+    RankWs w;
+    w.row_keys = c.take<unsigned long long>((size_t)(n_rows_local > 0 ? n_rows_local : 0) * 16);
+    w.gt_own = c.take<float>((size_t)(Nc > 0 ? Nc : 0) * 4);
+    c.take(256);
+    w.bytes = c.bytes;
+    return w;
 }
+extern "C" size_t itr_rank_workspace_bytes(int64_t n_rows_local, int64_t Nc) { return rank_ws(nullptr, n_rows_local, Nc).bytes; }
 
 extern "C" int itr_rank_counts(const float *S, int64_t ldS, int64_t row0, int64_t n_rows_local, int64_t Nc,
                                int im_div, const float *s_gt, int32_t *i2t_rank, int32_t *i2t_top1,
@@ -534,10 +540,9 @@ extern "C" int itr_rank_counts(const float *S, int64_t ldS, int64_t row0, int64_
     ITR_REQUIRE(workspace && workspace_bytes >= itr_rank_workspace_bytes(n_rows_local, Nc) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
                 "itr_rank_counts: workspace missing, misaligned or smaller than itr_rank_workspace_bytes");
     hipStream_t st = itr::as_stream(stream);
-    char *wp = static_cast<char *>(workspace);
-    unsigned long long *row_gkey = reinterpret_cast<unsigned long long *>(wp), *row_best = row_gkey + n_rows_local;
-    wp += rank_al((size_t)n_rows_local * 16);
-    float *gt_own = reinterpret_cast<float *>(wp);
+    const RankWs ws = rank_ws(workspace, n_rows_local, Nc);
+    unsigned long long *row_gkey = ws.row_keys, *row_best = row_gkey + n_rows_local;
+    float *gt_own = ws.gt_own;
     // rows per workgroup: the smallest multiple of 64 for which the grid fits the chip's resident workgroups in one round
     int64_t slots = 0;
     {

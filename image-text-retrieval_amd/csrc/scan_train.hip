@@ -16,6 +16,7 @@
 // second kernel), d||e_w|| partial (summed over images by itr_colsum).  The D-long contractions of the backward are
 // again plain GEMMs done by the caller:  dV = dA E + (dG + dG^T) V,   dE = dA^T V + d||e|| e / ||e||.
 #include "scan_common.h"
+#include "itr_internal.h"
 #include <mutex>
 #include <set>
 #include <utility>
@@ -360,10 +361,6 @@ __global__ __launch_bounds__(256) void enorm_bwd_kernel(const float *__restrict_
     if (n > 0.f) dE[row * D + d] += den[row] * E[row * D + d] / n;
 }
 
-// LDS-tiled Gram kernel of the evaluation path (scan_xattn.hip): G[n] = X_n X_n^T
-__global__ void gram_kernel(const float *__restrict__ X, const int64_t *__restrict__ row_off, const int32_t *__restrict__ row_cnt, int fixed_rows,
-                            int D, float *__restrict__ G, const int64_t *__restrict__ g_off, int upper2);
-__global__ void gram_mfma_kernel(const float *__restrict__ X, int rows, int D, float *__restrict__ G, int upper2);
 
 static int check_train_args(const char *who, int64_t Bi, int64_t Bc, int64_t n_tok, int R, int D, int norm, int agg, int max_len) {
     ITR_REQUIRE(Bi >= 1 && Bc >= 1 && n_tok >= 1 && D > 0, "%s: bad shape", who);

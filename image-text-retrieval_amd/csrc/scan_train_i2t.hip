@@ -10,6 +10,7 @@
 // d||v_r|| partial (summed over captions by itr_colsum).  Caller:  dV = dA E + d||v|| v / ||v||,
 // dE = dA^T V + (dH + dH^T) E_c.
 #include "scan_common.h"
+#include "itr_internal.h"
 
 namespace itr {
 
@@ -322,7 +323,6 @@ __global__ __launch_bounds__(256) void caption_gram_kernel(const float *__restri
     }
 }
 
-int allow_dynamic_lds(const void *kernel, size_t bytes);      // scan_train.hip
 
 static int check_i2t(const char *who, int64_t Bi, int64_t Bc, int64_t n_tok, int R, int D, int norm, int agg, int max_len) {
     ITR_REQUIRE(Bi >= 1 && Bc >= 1 && n_tok >= 1 && D > 0, "%s: bad shape", who);

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "scan_common.h"
+#include "itr_internal.h"
 #include "pack_plan.h"
 
 namespace itr {
@@ -907,37 +908,22 @@ __global__ __launch_bounds__(256) void scan_split_rows_kernel(const float *__res
     *reinterpret_cast<uint2 *>(o + 32) = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 static_assert(sizeof(ScanSmem) <= 80 * 1024, "two workgroups per CU need <= 80 KiB of LDS each");
 
-// Workspace layout (prepare and scores agree on it)
-struct ScanWs {
-    float *gram, *wnorm, *vnorm, *cgram, *hblk, *wtiled;
-    int64_t *coff;
-    ScanTileMeta *meta;
-};
-static size_t scan_ws_bytes(int64_t Ni, int R, int64_t n_rows, int64_t Nc, int64_t n_tiles, int D) {
-    const size_t common = align256((size_t)n_tiles * sizeof(ScanTileMeta)) + align256((size_t)n_tiles * SC_NT * D * 4);
-    const size_t t2i = align256((size_t)Ni * R * R * 4) + align256((size_t)n_tiles * SC_NT * 4);
-    const size_t i2t = align256((size_t)Ni * R * 4) + align256((size_t)Nc * 8) + align256((size_t)n_rows * SC_NT * 4) +
-                       align256((size_t)n_tiles * SC_NT * SC_NT * 4);
-    return common + (t2i > i2t ? t2i : i2t);
-}
-static ScanWs scan_carve(void *workspace, int64_t Ni, int R, int64_t n_rows, int64_t Nc, int64_t n_tiles, int D, int mode) {
-    char *ws = static_cast<char *>(workspace);
-    ScanWs w{};
-    w.meta = reinterpret_cast<ScanTileMeta *>(ws); ws += align256((size_t)n_tiles * sizeof(ScanTileMeta));
-    w.wtiled = reinterpret_cast<float *>(ws); ws += align256((size_t)n_tiles * SC_NT * D * 4);
-    if (mode == 0) {
-        w.gram = reinterpret_cast<float *>(ws); ws += align256((size_t)Ni * R * R * 4);
-        w.wnorm = reinterpret_cast<float *>(ws);
-    } else {
-        w.vnorm = reinterpret_cast<float *>(ws); ws += align256((size_t)Ni * R * 4);
-        w.coff = reinterpret_cast<int64_t *>(ws); ws += align256((size_t)Nc * 8);
-        w.cgram = reinterpret_cast<float *>(ws); ws += align256((size_t)n_rows * SC_NT * 4);
-        w.hblk = reinterpret_cast<float *>(ws);
-    }
-    return w;
+// Workspace layout (prepare, scores and SGRAF agree on it): the size covers both modes, the pointers are those of `mode`
+ScanWs scan_ws(void *base, int64_t Ni, int R, int64_t n_rows, int64_t Nc, int64_t n_tiles, int D, int mode) {
+    WsCarver c(base);
+    ScanWs s{};
+    s.meta = c.take<ScanTileMeta>((size_t)n_tiles * sizeof(ScanTileMeta));
+    s.wtiled = c.take<float>((size_t)n_tiles * SC_NT * D * 4);
+    WsCarver t2i = c, i2t = c;      // the two modes' buffers share the rest
+    ScanWs a = s, b = s;
+    a.gram = t2i.take<float>((size_t)Ni * R * R * 4), a.wnorm = t2i.take<float>((size_t)n_tiles * SC_NT * 4);
+    b.vnorm = i2t.take<float>((size_t)Ni * R * 4), b.coff = i2t.take<int64_t>((size_t)Nc * 8);
+    b.cgram = i2t.take<float>((size_t)n_rows * SC_NT * 4), b.hblk = i2t.take<float>((size_t)n_tiles * SC_NT * SC_NT * 4);
+    s = mode == 0 ? a : b;
+    s.bytes = t2i.bytes > i2t.bytes ? t2i.bytes : i2t.bytes;
+    return s;
 }
 
 }  // namespace itr
@@ -972,7 +958,7 @@ extern "C" int itr_scan_plan_tiles(const int32_t *len_host, int64_t Nc, int nt, 
 }
 
 extern "C" size_t itr_scan_workspace_bytes(int64_t Ni, int R, int64_t n_rows, int64_t Nc, int64_t n_tiles, int D) {
-    return itr::scan_ws_bytes(Ni, R, n_rows, Nc, n_tiles, D);
+    return itr::scan_ws(nullptr, Ni, R, n_rows, Nc, n_tiles, D, 0).bytes;
 }
 
 namespace itr {
@@ -988,10 +974,10 @@ int scan_prepare_impl(const float *img, const float *words, const int64_t *cap_o
     ITR_UNSUPPORTED(D % SC_BK != 0, "itr_scan_prepare: embed dim must be a multiple of %d, got %d", SC_BK, D);
     ITR_REQUIRE((reinterpret_cast<uintptr_t>(img) & 15) == 0 && (reinterpret_cast<uintptr_t>(words) & 15) == 0,
                 "itr_scan_prepare: operands must be 16-byte aligned");
-    ITR_REQUIRE(workspace_bytes >= scan_ws_bytes(Ni, R, n_rows, Nc, n_tiles, D), "itr_scan_prepare: workspace too small");
+    const ScanWs w = scan_ws(workspace, Ni, R, n_rows, Nc, n_tiles, D, mode);
+    ITR_REQUIRE(workspace_bytes >= w.bytes, "itr_scan_prepare: workspace too small");
     if (Ni == 0 || Nc == 0) return ITR_OK;
     hipStream_t st = as_stream(stream);
-    ScanWs w = scan_carve(workspace, Ni, R, n_rows, Nc, n_tiles, D, mode);
     hipLaunchKernelGGL(scan_pack_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, words, cap_off, cap_len,
                        tile_begin_dev, cap_order_dev, D, w.wtiled, w.meta, w.wnorm, cap_col);
     ITR_CHECK_LAUNCH("scan pack");
@@ -1034,8 +1020,6 @@ static int scan_scores_impl2(const float *img, int64_t n_tiles, int64_t Ni, int6
                              void *workspace, size_t workspace_bytes, float *emit_p, float *emit_cn, int64_t img_index0,
                              int64_t img_count, void *bf16_ws, int f16, itr_stream_t stream, int debug_bits = 0);
 
-int allow_dynamic_lds(const void *kernel, size_t bytes);      // scan_train.hip
-
 int scan_scores_impl(const float *img, int64_t n_tiles, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D,
                      int mode, int norm, int agg, float lambda_softmax, float lambda_lse, float *S, int64_t ldS,
                      void *workspace, size_t workspace_bytes, float *emit_p, float *emit_cn, int64_t img_index0,
@@ -1044,8 +1028,14 @@ int scan_scores_impl(const float *img, int64_t n_tiles, int64_t Ni, int64_t Nc, 
                              workspace_bytes, emit_p, emit_cn, img_index0, img_count, nullptr, 0, stream);
 }
 
-static size_t scan_bf16_ws_bytes(int64_t Ni, int R, int64_t n_tiles, int D) {
-    return align256((size_t)Ni * R * D * 4) + align256((size_t)n_tiles * SC_NT * D * 4);
+// the split-bf16 operands: hi / lo halves of the images' rows, then of the packed word tiles' rows
+struct ScanBf16Ws { uint16_t *img, *wt; size_t bytes; };
+static ScanBf16Ws scan_bf16_ws(void *base, int64_t Ni, int R, int64_t n_tiles, int D) {
+    WsCarver c(base);
+    ScanBf16Ws w;
+    w.img = c.take<uint16_t>((size_t)Ni * R * D * 4), w.wt = c.take<uint16_t>((size_t)n_tiles * SC_NT * D * 4);
+    w.bytes = c.bytes;
+    return w;
 }
 
 // bf16_ws != null: the split-bf16 ("bf16x3") main loop; img and the packed word tiles are split into bf16_ws first
@@ -1062,12 +1052,11 @@ static int scan_scores_impl2(const float *img, int64_t n_tiles, int64_t Ni, int6
     ITR_UNSUPPORTED(D <= 0 || D % SC_BK != 0, "itr_scan_xattn_scores: embed dim must be a multiple of %d, got %d",
                     SC_BK, D);
     ITR_REQUIRE((reinterpret_cast<uintptr_t>(img) & 15) == 0, "itr_scan_xattn_scores: operands must be 16-byte aligned");
-    ITR_REQUIRE(workspace_bytes >= scan_ws_bytes(Ni, R, n_rows, Nc, n_tiles, D),
-                "itr_scan_xattn_scores: workspace too small");
+    const ScanWs w = scan_ws(workspace, Ni, R, n_rows, Nc, n_tiles, D, mode);
+    ITR_REQUIRE(workspace_bytes >= w.bytes, "itr_scan_xattn_scores: workspace too small");
     if (Ni == 0 || Nc == 0) return ITR_OK;
     hipStream_t st = as_stream(stream);
 
-    ScanWs w = scan_carve(workspace, Ni, R, n_rows, Nc, n_tiles, D, mode);
     ScanArgs a{};
     a.img = img; a.wtiled = w.wtiled; a.meta = w.meta;
     a.S = S; a.ldS = ldS; a.Ni = Ni; a.Nc = Nc; a.n_tiles = n_tiles; a.D = D;
@@ -1111,8 +1100,8 @@ static int scan_scores_impl2(const float *img, int64_t n_tiles, int64_t Ni, int6
     if (bf16_ws) {
         ITR_UNSUPPORTED((uint64_t)Ni * R * D * 4 >= (1ull << 32) || (uint64_t)SC_NT * D * 4 >= (1ull << 32),
                         "itr_scan_xattn_scores_bf16x3: per-launch operand offsets must fit 32 bits; shard the images");
-        uint16_t *img_bf = static_cast<uint16_t *>(bf16_ws);
-        uint16_t *wt_bf = reinterpret_cast<uint16_t *>(static_cast<char *>(bf16_ws) + align256((size_t)Ni * R * D * 4));
+        const ScanBf16Ws bw = scan_bf16_ws(bf16_ws, Ni, R, n_tiles, D);      // (Ni: the images of this call's sub-range)
+        uint16_t *img_bf = bw.img, *wt_bf = bw.wt;
         const dim3 sg((unsigned)ceil_div(D / 4, 256), 1);
         ITR_REQUIRE(Ni * R <= 0x7fffffff / 1 && n_tiles * SC_NT <= 0x7fffffff, "scan split: too many rows");
         for (int64_t r0 = 0; r0 < Ni * R; r0 += 65535)
@@ -1159,14 +1148,14 @@ extern "C" int itr_scan_xattn_scores(const float *img, int64_t n_tiles, int64_t 
 }
 
 extern "C" size_t itr_scan_bf16_workspace_bytes(int64_t Ni, int R, int64_t n_tiles, int D) {
-    return itr::scan_bf16_ws_bytes(Ni, R, n_tiles, D);
+    return itr::scan_bf16_ws(nullptr, Ni, R, n_tiles, D).bytes;
 }
 
 extern "C" int itr_scan_xattn_scores_bf16x3(const float *img, int64_t n_tiles, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D,
                                             int mode, int norm, int agg, float lambda_softmax, float lambda_lse, float *S,
                                             int64_t ldS, void *workspace, size_t workspace_bytes, void *bf16_workspace,
                                             size_t bf16_workspace_bytes, int split_format, itr_stream_t stream) {
-    ITR_REQUIRE(bf16_workspace && bf16_workspace_bytes >= itr::scan_bf16_ws_bytes(Ni, R, n_tiles, D),
+    ITR_REQUIRE(bf16_workspace && bf16_workspace_bytes >= itr::scan_bf16_ws(nullptr, Ni, R, n_tiles, D).bytes,
                 "itr_scan_xattn_scores_bf16x3: split workspace missing or too small");
     ITR_REQUIRE(split_format == 0 || split_format == 1, "itr_scan_xattn_scores_bf16x3: split_format 0 (bf16) or 1 (fp16)");
     return itr::scan_scores_impl2(img, n_tiles, Ni, Nc, n_rows, R, D, mode, norm, agg, lambda_softmax, lambda_lse, S, ldS, workspace,

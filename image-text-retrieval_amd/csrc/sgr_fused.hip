@@ -33,6 +33,7 @@
 // classes ON THE DEVICE (sgr_group_meta_kernel + sgr_group_classify_kernel: no host round trip); a class's persistent launch reads
 // its item count from device memory.
 #include "scan_common.h"
+#include "itr_internal.h"
 #include "pack_plan.h"
 #include <string.h>
 #include <stdlib.h>
@@ -950,17 +951,17 @@ struct SgrWs {
     size_t bytes;
 };
 static SgrWs sgr_carve(void *ws, int64_t n_groups, int64_t n_caps, int sgr_step) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    char *p = static_cast<char *>(ws);
+    WsCarver c(ws);
     SgrWs w;
-    w.meta = reinterpret_cast<SgrGroupMeta *>(p); p += al((size_t)n_groups * sizeof(SgrGroupMeta));
-    w.cls = reinterpret_cast<int8_t *>(p); p += al((size_t)n_groups);
-    w.glist = reinterpret_cast<int32_t *>(p); p += al((size_t)2 * n_groups * 4);
-    w.gcount = reinterpret_cast<int32_t *>(p); p += 256;
-    w.cap_bad = reinterpret_cast<int32_t *>(p); p += al((size_t)n_caps * 4);
-    w.frag = reinterpret_cast<float4 *>(p); p += (size_t)sgr_step * 2 * SF_S * SF_S * 4;
-    w.wT = reinterpret_cast<float *>(p); p += (size_t)SF_S * SF_S * 4;
-    w.bytes = (size_t)(p - static_cast<char *>(ws)) + 256;
+    w.meta = c.take<SgrGroupMeta>((size_t)n_groups * sizeof(SgrGroupMeta));
+    w.cls = c.take<int8_t>((size_t)n_groups);
+    w.glist = c.take<int32_t>((size_t)2 * n_groups * 4);
+    w.gcount = c.take<int32_t>(256);
+    w.cap_bad = c.take<int32_t>((size_t)n_caps * 4);
+    w.frag = c.take<float4>((size_t)sgr_step * 2 * SF_S * SF_S * 4);
+    w.wT = c.take<float>((size_t)SF_S * SF_S * 4);
+    c.take(256);
+    w.bytes = c.bytes;
     return w;
 }
 size_t sgr_fused_workspace_bytes(int64_t n_groups, int64_t n_caps, int sgr_step) { return sgr_carve(nullptr, n_groups, n_caps, sgr_step).bytes; }
@@ -994,7 +995,6 @@ int sgr_fused_finish(void *ws, int64_t n_groups, int64_t n_caps, int sgr_step, i
     return ITR_OK;
 }
 
-int allow_dynamic_lds(const void *kernel, size_t bytes);      // scan_train.hip: once per (kernel, device), under a mutex
 
 static int sgr_cu_count(int64_t *cus) {
     static int cus_of[64] = {};

@@ -11,33 +11,10 @@
 //      (q' = (Wk^T Wq) x + Wk^T bq, see below), MFMA pair kernel softmax(q' X^T) X, graph GEMM; sigmoid(sim_eval_w) (:443-444)
 // The global nodes img_glo / cap_glo (VisualSA :491-507, TextSA :543-559) are computed once per call.
 #include "scan_common.h"
+#include "itr_internal.h"
 #include <stdlib.h>
 
 namespace itr {
-
-int gemm_nt(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc,
-            int64_t M, int64_t N, int64_t K, int act, hipStream_t st);
-int gemm_nt_sqdiff(const float *A, int64_t lda, const float *B, int64_t ldb, const float *rowscale, const float *Z,
-                   int64_t ldz, float *C, int64_t ldc, int64_t M, int64_t N, int64_t K, hipStream_t st);
-int norm_rows(const float *x, float *y, int64_t rows, int dim, float eps, int kind, int take_abs, hipStream_t st);
-int scan_prepare_impl(const float *img, const float *words, const int64_t *cap_off, const int32_t *cap_len,
-                      const int32_t *tile_begin_dev, const int32_t *cap_order_dev, int64_t n_tiles, int64_t Ni,
-                      int64_t Nc, int64_t n_rows, int R, int D, int mode, void *workspace, size_t workspace_bytes,
-                      int32_t *cap_col, itr_stream_t stream);
-int scan_scores_impl(const float *img, int64_t n_tiles, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D,
-                     int mode, int norm, int agg, float lambda_softmax, float lambda_lse, float *S, int64_t ldS,
-                     void *workspace, size_t workspace_bytes, float *emit_p, float *emit_cn, int64_t img_index0,
-                     int64_t img_count, itr_stream_t stream);
-
-int sgraf_loc_fused(const float *P, const float *cn, const float *img, const float *wtiled, const float *W, const float *bias,
-                    float *X, int64_t nb, int64_t n_tiles, int D, hipStream_t st);
-// sgr_fused.hip: all graph-reasoning steps of a group of captions in one workgroup
-size_t sgr_fused_workspace_bytes(int64_t n_groups, int64_t n_caps, int sgr_step);
-int sgr_fused_prepare(const int32_t *grp_begin, const int32_t *grp_order, int64_t n_groups, int64_t n_caps, const int32_t *cap_len,
-                      const int32_t *cap_col, const float *const *wq, const float *const *wg, int sgr_step, void *ws, int *bad_flag, hipStream_t st);
-int sgr_fused_scores(const float *xloc, const float *xglo, void *ws, int64_t n_groups, int64_t n_caps, int64_t nb, int64_t Nc, int64_t ncols,
-                     const float *const *vq, const float *const *bg, int sgr_step, float *y0, bool persistent_walk, hipStream_t st);
-int sgr_fused_finish(void *ws, int64_t n_groups, int64_t n_caps, int sgr_step, int64_t Ni, float *S, int64_t ldS, hipStream_t st);
 
 constexpr float BN_EPS = 1e-5f;
 
@@ -412,7 +389,6 @@ __global__ __launch_bounds__(256) void sgr_final_kernel(const float *__restrict_
     if (lane == 0) S[(img_index0 + pair / Nc) * ldS + pair % Nc] = 1.f / (1.f + expf(-s));
 }
 
-static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 // Images per block of the pair stage (a multiple of the SCAN image tile).  64 by default since round 4 (rounds 1-3: 16) -- a quarter of
 // the launches, and the persistent SGR kernel's tail (the last, partial round of items over the CUs) is a quarter as large: SGR 1k x 5k
 // 735.8 -> 723.5 ms, SAF 373.3 -> 371.3 (same box; 32: 732.9 / 372.7).  The workspace grows with it (5k x 25k at 64: SAF 38 GB, SGR
@@ -441,29 +417,57 @@ static inline bool sgraf_needs_aglo(int S) {
 // the fused graph steps need neither the query nor the aggregate rows of the word nodes in memory (they live in the workgroup's LDS)
 static inline bool sgraf_fused_layout(int module, int S, int flags) { return module == 1 && S == 256 && !(flags & ITR_SGRAF_UNFUSED_STEPS); }
 
+// Workspace layout of itr_sgraf_scores (a null pointer: the block is not part of this layout)
+struct SgrafWs {
+    void *scan;                  // the SCAN workspace, then 256 bytes
+    size_t scan_bytes;
+    float *img_ave, *g_emb_v, *img_glo, *l_emb_v, *imgT, *l_emb_t, *cap_ave, *g_emb_t, *cap_glo;
+    int32_t *cap_col;
+    float *P, *cn, *sscr, *Aloc, *Aglo, *Pg, *cng, *gimg, *Xloc, *Xglo;      // (sscr: SCAN scores, not read)
+    float *Qloc, *Qglo, *Yloc, *Yglo, *WqT, *WkT, *Wfold[8], *vfold[8];
+    void *fused_ws;              // fused SGR: group records, weight fragments; then its flag
+    int *fused_bad;
+    size_t bytes;
+};
+static SgrafWs sgraf_ws(void *base, int64_t Ni, int64_t Nc, int64_t n_rows, int64_t n_tiles, int D, int S, int module, int image_block, int flags) {
+    const int64_t ncols = n_tiles * SC_NT, IB = sgraf_ib(S, Ni, image_block), NcP = (Nc + SC_NT - 1) / SC_NT * SC_NT;   // NcP: whole 64-row tiles
+    WsCarver c(base);
+    SgrafWs t{};
+    t.scan_bytes = scan_ws(nullptr, Ni, SC_R, n_rows, Nc, n_tiles, D, 0).bytes;
+    t.scan = c.take(t.scan_bytes + 256);
+    t.img_ave = c.take<float>((size_t)Ni * D * 4), t.g_emb_v = c.take<float>((size_t)Ni * D * 4), t.img_glo = c.take<float>((size_t)Ni * D * 4);
+    t.l_emb_v = c.take<float>((size_t)Ni * SC_R * D * 4), t.imgT = c.take<float>((size_t)Ni * SC_R * D * 4);
+    t.l_emb_t = c.take<float>((size_t)n_rows * D * 4), t.cap_ave = c.take<float>((size_t)Nc * D * 4), t.g_emb_t = c.take<float>((size_t)Nc * D * 4);
+    t.cap_glo = c.take<float>((size_t)NcP * D * 4);                             // + zero rows up to the last tile
+    t.cap_col = c.take<int32_t>((size_t)Nc * 4);
+    c.take((size_t)Nc * 8);                                                      // (unused slot)
+    t.P = c.take<float>((size_t)IB * ncols * SC_R * 4), t.cn = c.take<float>((size_t)IB * ncols * 4), t.sscr = c.take<float>((size_t)IB * Nc * 4);
+    if (S != 256) t.Aloc = c.take<float>((size_t)IB * ncols * D * 4);
+    if (sgraf_needs_aglo(S)) t.Aglo = c.take<float>((size_t)IB * Nc * D * 4);
+    t.Pg = c.take<float>((size_t)IB * NcP * SC_R * 4), t.cng = c.take<float>((size_t)IB * NcP * 4);   // one-hot weights, unit norms
+    t.gimg = c.take<float>((size_t)IB * SC_R * D * 4);                           // global "regions"
+    t.Xloc = c.take<float>((size_t)IB * ncols * S * 4), t.Xglo = c.take<float>((size_t)IB * NcP * S * 4);
+    if (module == 1) {
+        t.Yglo = c.take<float>((size_t)IB * NcP * S * 4);
+        if (!sgraf_fused_layout(module, S, flags)) {                             // step-by-step chain only
+            t.Qloc = c.take<float>((size_t)IB * ncols * S * 4), t.Yloc = c.take<float>((size_t)IB * ncols * S * 4);
+            t.Qglo = c.take<float>((size_t)IB * NcP * S * 4);
+        }
+        t.WqT = c.take<float>((size_t)S * S * 4), t.WkT = c.take<float>((size_t)S * S * 4);   // W^T scratch, folded query weights
+        for (int k = 0; k < 8; ++k) t.Wfold[k] = c.take<float>((size_t)S * S * 4), t.vfold[k] = c.take<float>((size_t)S * 4);
+        if (S == 256) t.fused_ws = c.take(sgr_fused_workspace_bytes(Nc, Nc, 8)), t.fused_bad = c.take<int>(256);   // (<= one group per caption)
+    }
+    // (the size has always counted cap_glo's zero tail as a block of its own)
+    c.take(align256((size_t)Nc * D * 4) + align256((size_t)(NcP - Nc) * D * 4) - align256((size_t)NcP * D * 4));
+    t.bytes = c.bytes;
+    return t;
+}
+
 }  // namespace itr
 
 extern "C" size_t itr_sgraf_workspace_bytes(int64_t Ni, int64_t Nc, int64_t n_rows, int64_t n_tiles, int D, int S,
                                             int module, int image_block, int flags) {
-    using namespace itr;
-    const int64_t ncols = n_tiles * SC_NT, IB = sgraf_ib(S, Ni, image_block);
-    const bool fused = sgraf_fused_layout(module, S, flags);
-    size_t b = itr_scan_workspace_bytes(Ni, SC_R, n_rows, Nc, n_tiles, D) + 256;
-    b += al((size_t)Ni * D * 4) * 3 + al((size_t)Ni * SC_R * D * 4) * 2;        // img_ave, g_emb_v, img_glo; l_emb_v, imgT
-    b += al((size_t)n_rows * D * 4) + al((size_t)Nc * D * 4) * 3;                // l_emb_t; cap_ave, g_emb_t, cap_glo
-    b += al((size_t)Nc * 4) + al((size_t)Nc * 8);                                // cap_col, seg offsets (unused slot)
-    b += al((size_t)IB * ncols * SC_R * 4) + al((size_t)IB * ncols * 4) + al((size_t)IB * Nc * 4);   // P, cn, scan scratch
-    const int64_t NcP = (Nc + SC_NT - 1) / SC_NT * SC_NT;                        // captions rounded up to whole 64-row tiles
-    b += (S == 256 ? 0 : al((size_t)IB * ncols * D * 4)) + (sgraf_needs_aglo(S) ? al((size_t)IB * Nc * D * 4) : 0);   // Aloc, Aglo (sim_dim != 256 only)
-    b += al((size_t)(NcP - Nc) * D * 4) + al((size_t)IB * NcP * SC_R * 4) + al((size_t)IB * NcP * 4) + al((size_t)IB * SC_R * D * 4);   // cap_glo tail, one-hot weights, unit norms, global "regions"
-    b += al((size_t)IB * ncols * S * 4) + al((size_t)IB * NcP * S * 4);         // Xloc, Xglo
-    if (module == 1) {
-        b += al((size_t)IB * NcP * S * 4);                                       // Yglo
-        if (!fused) b += al((size_t)IB * ncols * S * 4) * 2 + al((size_t)IB * NcP * S * 4);   // Qloc, Yloc, Qglo (step-by-step chain only)
-        b += al((size_t)S * S * 4) * 2 + (al((size_t)S * S * 4) + al((size_t)S * 4)) * 8;   // W^T scratch, folded query weights
-        if (S == 256) b += al(sgr_fused_workspace_bytes(Nc, Nc, 8)) + 256;       // group records (<= one per caption), weight fragments, flag
-    }
-    return b;
+    return itr::sgraf_ws(nullptr, Ni, Nc, n_rows, n_tiles, D, S, module, image_block, flags).bytes;
 }
 
 extern "C" int itr_sgraf_pick_image_block(int64_t Ni, int64_t Nc, int64_t n_rows, int64_t n_tiles, int D, int S, int module, int flags,
@@ -509,96 +513,57 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
     const bool have_plan = node_group_begin_dev && node_group_order_dev && n_node_groups > 0;
     if (module == 1 && S == 256 && !have_plan) flags |= ITR_SGRAF_UNFUSED_STEPS;      // no plan: the chain (and its larger workspace)
     const bool fused_sgr = sgraf_fused_layout(module, S, flags);      // (the step-by-step chain is the ABI flag ITR_SGRAF_UNFUSED_STEPS: layout and path agree)
-    ITR_REQUIRE(workspace_bytes >= itr_sgraf_workspace_bytes(Ni, Nc, n_rows, n_tiles, D, S, module, image_block, flags),
+    const SgrafWs ws = sgraf_ws(workspace, Ni, Nc, n_rows, n_tiles, D, S, module, image_block, flags);
+    ITR_REQUIRE(workspace_bytes >= ws.bytes,
                 "itr_sgraf_scores: workspace too small (size it with the same image_block and flags; without a node-group plan the step-by-step "
                 "chain runs: ITR_SGRAF_UNFUSED_STEPS)");
     if (Ni == 0 || Nc == 0) return ITR_OK;
     hipStream_t st = as_stream(stream);
     const int64_t ncols = n_tiles * SC_NT, IB = sgraf_ib(S, Ni, image_block);
-    const bool fused_layout = sgraf_fused_layout(module, S, flags);      // (what the workspace was sized for)
-
-    // ---- carve
-    char *p = static_cast<char *>(workspace);
-    auto take = [&](size_t bytes) { char *q = p; p += al(bytes); return q; };
-    const size_t scan_bytes = itr_scan_workspace_bytes(Ni, SC_R, n_rows, Nc, n_tiles, D);
-    void *scan_ws = take(scan_bytes + 256);
-    float *img_ave = (float *)take((size_t)Ni * D * 4), *g_emb_v = (float *)take((size_t)Ni * D * 4);
-    float *img_glo = (float *)take((size_t)Ni * D * 4);
-    float *l_emb_v = (float *)take((size_t)Ni * SC_R * D * 4), *imgT = (float *)take((size_t)Ni * SC_R * D * 4);
-    float *l_emb_t = (float *)take((size_t)n_rows * D * 4);
-    float *cap_ave = (float *)take((size_t)Nc * D * 4), *g_emb_t = (float *)take((size_t)Nc * D * 4);
     const int64_t NcP = (Nc + SC_NT - 1) / SC_NT * SC_NT;
     // sim_dim 256: the global nodes come from the local-node kernel (ITR_SGRAF_GLO_GEMM=1: the (a - b)^2 kernel + GEMM + l2norm chain
     // of rounds 1-2, for A/B timing); their rows then lie in whole 64-caption tiles: ldg = NcP rows per image
     const bool glo_loc = (S == 256) && !ITR_EXP_ENV("ITR_SGRAF_GLO_GEMM");
     const int64_t ldg = glo_loc ? NcP : Nc;
-    float *cap_glo = (float *)take((size_t)Nc * D * 4 + (size_t)(NcP - Nc) * D * 4);       // + zero rows up to the last tile
-    int32_t *cap_col = (int32_t *)take((size_t)Nc * 4);
-    take((size_t)Nc * 8);
-    float *P = (float *)take((size_t)IB * ncols * SC_R * 4), *cn = (float *)take((size_t)IB * ncols * 4);
-    float *sscr = (float *)take((size_t)IB * Nc * 4);
-    float *Aloc = (S == 256) ? nullptr : (float *)take((size_t)IB * ncols * D * 4);
-    float *Aglo = sgraf_needs_aglo(S) ? (float *)take((size_t)IB * Nc * D * 4) : nullptr;
-    float *Pg = (float *)take((size_t)IB * NcP * SC_R * 4), *cng = (float *)take((size_t)IB * NcP * 4);
-    float *gimg = (float *)take((size_t)IB * SC_R * D * 4);
-    float *Xloc = (float *)take((size_t)IB * ncols * S * 4), *Xglo = (float *)take((size_t)IB * NcP * S * 4);
-    float *Qloc = nullptr, *Qglo = nullptr, *Yloc = nullptr, *Yglo = nullptr;
-    float *WqT = nullptr, *WkT = nullptr, *Wfold[8] = {nullptr}, *vfold[8] = {nullptr};
-    if (module == 1) {
-        Yglo = (float *)take((size_t)IB * NcP * S * 4);
-        if (!fused_layout) {
-            Qloc = (float *)take((size_t)IB * ncols * S * 4); Yloc = (float *)take((size_t)IB * ncols * S * 4);
-            Qglo = (float *)take((size_t)IB * NcP * S * 4);
-        }
-        WqT = (float *)take((size_t)S * S * 4); WkT = (float *)take((size_t)S * S * 4);
-        for (int k = 0; k < 8; ++k) { Wfold[k] = (float *)take((size_t)S * S * 4); vfold[k] = (float *)take((size_t)S * 4); }
-    }
-    void *fused_ws = nullptr;
-    int *fused_bad = nullptr;
-    if (module == 1 && S == 256) {
-        fused_ws = take(sgr_fused_workspace_bytes(Nc, Nc, 8));
-        fused_bad = (int *)take(256);
-    }
     int rc;
 #define SG_TRY(x) { rc = (x); if (rc != ITR_OK) return rc; }
 
     // ---- global nodes: VisualSA (:491-507)
     ITR_REQUIRE(Ni <= 65535, "itr_sgraf_scores: at most 65535 images per call");
-    SG_TRY(itr_mean_mid(img, img_ave, Ni, SC_R, D, stream));
-    SG_TRY(gemm_nt(img, D, w->v_loc_w, D, w->v_loc_b, l_emb_v, D, Ni * SC_R, D, D, 0, st));
+    SG_TRY(itr_mean_mid(img, ws.img_ave, Ni, SC_R, D, stream));
+    SG_TRY(gemm_nt(img, D, w->v_loc_w, D, w->v_loc_b, ws.l_emb_v, D, Ni * SC_R, D, D, 0, st));
     {
         dim3 grid((unsigned)ceil_div(D, 256), (unsigned)1);
         // rows can exceed 65535: launch in slabs
         for (int64_t r0 = 0; r0 < Ni * SC_R; r0 += 65520) {   // 65520 is a multiple of 36
             const int64_t nr = (Ni * SC_R - r0 < 65520) ? Ni * SC_R - r0 : 65520;
             hipLaunchKernelGGL(bn_tanh_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)nr), dim3(256), 0, st,
-                               l_emb_v + r0 * D, nr, D, 1, SC_R, w->v_loc_bn_w, w->v_loc_bn_b, w->v_loc_bn_mean, w->v_loc_bn_var);
+                               ws.l_emb_v + r0 * D, nr, D, 1, SC_R, w->v_loc_bn_w, w->v_loc_bn_b, w->v_loc_bn_mean, w->v_loc_bn_var);
         }
         ITR_CHECK_LAUNCH("sgraf bn_tanh (local)");
         (void)grid;
     }
-    SG_TRY(gemm_nt(img_ave, D, w->v_glo_w, D, w->v_glo_b, g_emb_v, D, Ni, D, D, 0, st));
-    hipLaunchKernelGGL(bn_tanh_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)Ni), dim3(256), 0, st, g_emb_v, Ni, D, 0, 1,
+    SG_TRY(gemm_nt(ws.img_ave, D, w->v_glo_w, D, w->v_glo_b, ws.g_emb_v, D, Ni, D, D, 0, st));
+    hipLaunchKernelGGL(bn_tanh_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)Ni), dim3(256), 0, st, ws.g_emb_v, Ni, D, 0, 1,
                        w->v_glo_bn_w, w->v_glo_bn_b, w->v_glo_bn_mean, w->v_glo_bn_var);
     ITR_CHECK_LAUNCH("sgraf bn_tanh (global)");
-    hipLaunchKernelGGL(sa_pool_kernel, dim3((unsigned)Ni), dim3(256), 0, st, img, l_emb_v, g_emb_v, w->v_com_w, w->v_com_b,
-                       (const int64_t *)nullptr, (const int32_t *)nullptr, SC_R, D, img_glo);
+    hipLaunchKernelGGL(sa_pool_kernel, dim3((unsigned)Ni), dim3(256), 0, st, img, ws.l_emb_v, ws.g_emb_v, w->v_com_w, w->v_com_b,
+                       (const int64_t *)nullptr, (const int32_t *)nullptr, SC_R, D, ws.img_glo);
     ITR_CHECK_LAUNCH("sgraf sa_pool (image)");
     // ---- TextSA (:543-559)
-    SG_TRY(gemm_nt(words, D, w->t_loc_w, D, w->t_loc_b, l_emb_t, D, n_rows, D, D, 2 /*tanh*/, st));
-    hipLaunchKernelGGL(seg_mean_kernel, dim3((unsigned)Nc), dim3(256), 0, st, words, cap_off, cap_len, D, cap_ave);
+    SG_TRY(gemm_nt(words, D, w->t_loc_w, D, w->t_loc_b, ws.l_emb_t, D, n_rows, D, D, 2 /*tanh*/, st));
+    hipLaunchKernelGGL(seg_mean_kernel, dim3((unsigned)Nc), dim3(256), 0, st, words, cap_off, cap_len, D, ws.cap_ave);
     ITR_CHECK_LAUNCH("sgraf seg_mean");
-    SG_TRY(gemm_nt(cap_ave, D, w->t_glo_w, D, w->t_glo_b, g_emb_t, D, Nc, D, D, 2, st));
-    hipLaunchKernelGGL(sa_pool_kernel, dim3((unsigned)Nc), dim3(256), 0, st, words, l_emb_t, g_emb_t, w->t_com_w, w->t_com_b, cap_off,
-                       cap_len, 0, D, cap_glo);
+    SG_TRY(gemm_nt(ws.cap_ave, D, w->t_glo_w, D, w->t_glo_b, ws.g_emb_t, D, Nc, D, D, 2, st));
+    hipLaunchKernelGGL(sa_pool_kernel, dim3((unsigned)Nc), dim3(256), 0, st, words, ws.l_emb_t, ws.g_emb_t, w->t_com_w, w->t_com_b, cap_off,
+                       cap_len, 0, D, ws.cap_glo);
     ITR_CHECK_LAUNCH("sgraf sa_pool (caption)");
     // ---- operand prep for the pair stage
-    hipLaunchKernelGGL(transpose_img_kernel, dim3((unsigned)ceil_div(D, 64), (unsigned)Ni), dim3(256), 0, st, img, SC_R, D, imgT);
+    hipLaunchKernelGGL(transpose_img_kernel, dim3((unsigned)ceil_div(D, 64), (unsigned)Ni), dim3(256), 0, st, img, SC_R, D, ws.imgT);
     ITR_CHECK_LAUNCH("sgraf transpose");
     SG_TRY(scan_prepare_impl(img, words, cap_off, cap_len, tile_begin_dev, cap_order_dev, n_tiles, Ni, Nc, n_rows, SC_R, D, 0,
-                             scan_ws, scan_bytes, cap_col, stream));
-    // the tile-packed words live at a fixed place of the scan workspace (scan_carve: meta first, then wtiled)
-    const float *wtiled = reinterpret_cast<const float *>(static_cast<char *>(scan_ws) + al((size_t)n_tiles * sizeof(ScanTileMeta)));
+                             ws.scan, ws.scan_bytes, ws.cap_col, stream));
+    const float *wtiled = scan_ws(ws.scan, Ni, SC_R, n_rows, Nc, n_tiles, D, 0).wtiled;      // (the tile-packed words)
 
     // ---- SGR: fold the key projection into the query projection (GraphReasoning, Fusionmodule.py:589-597).
     // edge = softmax_j(q_i . k_j) with q = Wq x + bq, k = Wk x + bk.  q_i . k_j = (Wk^T q_i) . x_j + q_i . bk and the
@@ -608,12 +573,12 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
     if (module == 1) {
         const unsigned tb = (unsigned)ceil_div((int64_t)S * S, 256);
         for (int k = 0; k < sgr_step; ++k) {
-            hipLaunchKernelGGL(transpose_small_kernel, dim3(tb), dim3(256), 0, st, w->sgr_q_w[k], S, S, WqT);
-            hipLaunchKernelGGL(transpose_small_kernel, dim3(tb), dim3(256), 0, st, w->sgr_k_w[k], S, S, WkT);
+            hipLaunchKernelGGL(transpose_small_kernel, dim3(tb), dim3(256), 0, st, w->sgr_q_w[k], S, S, ws.WqT);
+            hipLaunchKernelGGL(transpose_small_kernel, dim3(tb), dim3(256), 0, st, w->sgr_k_w[k], S, S, ws.WkT);
             ITR_CHECK_LAUNCH("sgraf weight transpose");
             // Wfold[b][a] = sum_o Wk[o][b] Wq[o][a];  vfold[b] = sum_o bq[o] Wk[o][b]
-            SG_TRY(gemm_nt(WkT, S, WqT, S, nullptr, Wfold[k], S, S, S, S, 0, st));
-            SG_TRY(gemm_nt(w->sgr_q_b[k], S, WkT, S, nullptr, vfold[k], S, 1, S, S, 0, st));
+            SG_TRY(gemm_nt(ws.WkT, S, ws.WqT, S, nullptr, ws.Wfold[k], S, S, S, S, 0, st));
+            SG_TRY(gemm_nt(w->sgr_q_b[k], S, ws.WkT, S, nullptr, ws.vfold[k], S, 1, S, S, 0, st));
         }
     }
 
@@ -621,47 +586,47 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
         // rows of captions Nc .. NcP - 1 (and of refused groups) are never written by the pair / fused kernels but run through the GEMMs of
         // the steps: defined values, not uninitialised workspace
         // (Qglo -- step-by-step chain only -- is a GEMM output: every row the pair kernel reads is written first)
-        ITR_CHECK_HIP(hipMemsetAsync(Yglo, 0, (size_t)IB * NcP * S * 4, st));
+        ITR_CHECK_HIP(hipMemsetAsync(ws.Yglo, 0, (size_t)IB * NcP * S * 4, st));
     }
     if (fused_sgr) {
-        ITR_CHECK_HIP(hipMemsetAsync(fused_bad, 0, sizeof(int), st));
-        SG_TRY(sgr_fused_prepare(node_group_begin_dev, node_group_order_dev, n_node_groups, Nc, cap_len, cap_col, Wfold, w->sgr_g_w, sgr_step,
-                                 fused_ws, fused_bad, st));
+        ITR_CHECK_HIP(hipMemsetAsync(ws.fused_bad, 0, sizeof(int), st));
+        SG_TRY(sgr_fused_prepare(node_group_begin_dev, node_group_order_dev, n_node_groups, Nc, cap_len, ws.cap_col, ws.Wfold, w->sgr_g_w, sgr_step,
+                                 ws.fused_ws, ws.fused_bad, st));
     }
 
     if (glo_loc) {
-        if (NcP > Nc) ITR_CHECK_HIP(hipMemsetAsync(cap_glo + Nc * D, 0, (size_t)(NcP - Nc) * D * 4, st));
-        ITR_CHECK_HIP(hipMemsetAsync(gimg, 0, (size_t)IB * SC_R * D * 4, st));
-        hipLaunchKernelGGL(glo_onehot_kernel, dim3((unsigned)ceil_div(IB * NcP * SC_R, (int64_t)256)), dim3(256), 0, st, Pg, cng, IB * NcP);
+        if (NcP > Nc) ITR_CHECK_HIP(hipMemsetAsync(ws.cap_glo + Nc * D, 0, (size_t)(NcP - Nc) * D * 4, st));
+        ITR_CHECK_HIP(hipMemsetAsync(ws.gimg, 0, (size_t)IB * SC_R * D * 4, st));
+        hipLaunchKernelGGL(glo_onehot_kernel, dim3((unsigned)ceil_div(IB * NcP * SC_R, (int64_t)256)), dim3(256), 0, st, ws.Pg, ws.cng, IB * NcP);
         ITR_CHECK_LAUNCH("sgraf glo one-hot");
     }
-    PairArgs pa{Xglo, Xloc, cap_col, cap_len, Nc, ncols, S, ldg};
+    PairArgs pa{ws.Xglo, ws.Xloc, ws.cap_col, cap_len, Nc, ncols, S, ldg};
     for (int64_t i0 = 0; i0 < Ni; i0 += IB) {
         const int64_t nb = (Ni - i0 < IB) ? Ni - i0 : IB;
         // 1. attention weights + context norms  (SCAN_attention: clipped_l2norm, smooth 9)
-        SG_TRY(scan_scores_impl(img, n_tiles, Ni, Nc, n_rows, SC_R, D, 0, 0, 0, 9.0f, 6.0f, sscr, Nc, scan_ws, scan_bytes, P, cn, i0,
+        SG_TRY(scan_scores_impl(img, n_tiles, Ni, Nc, n_rows, SC_R, D, 0, 0, 0, 9.0f, 6.0f, ws.sscr, Nc, ws.scan, ws.scan_bytes, ws.P, ws.cn, i0,
                                 nb, stream));
         // 2. (l2norm(ctx) - E)^2 per image, 3. sim_loc
         if (S == 256) {   // the configured sim_dim: fused, (ctx - E)^2 never leaves the chip (sgraf_loc.hip)
-            SG_TRY(sgraf_loc_fused(P, cn, img + i0 * SC_R * D, wtiled, w->loc_w, w->loc_b, Xloc, nb, n_tiles, D, st));
+            SG_TRY(sgraf_loc_fused(ws.P, ws.cn, img + i0 * SC_R * D, wtiled, w->loc_w, w->loc_b, ws.Xloc, nb, n_tiles, D, st));
         } else {
             for (int64_t ii = 0; ii < nb; ++ii)
-                SG_TRY(gemm_nt_sqdiff(P + ii * ncols * SC_R, SC_R, imgT + (i0 + ii) * D * SC_R, SC_R, cn + ii * ncols, wtiled, D,
-                                      Aloc + ii * ncols * D, D, ncols, D, SC_R, st));
-            SG_TRY(gemm_nt(Aloc, D, w->loc_w, D, w->loc_b, Xloc, S, nb * ncols, S, D, 0, st));
-            SG_TRY(norm_rows(Xloc, Xloc, nb * ncols, S, 1e-8f, 0, 0, st));
+                SG_TRY(gemm_nt_sqdiff(ws.P + ii * ncols * SC_R, SC_R, ws.imgT + (i0 + ii) * D * SC_R, SC_R, ws.cn + ii * ncols, wtiled, D,
+                                      ws.Aloc + ii * ncols * D, D, ncols, D, SC_R, st));
+            SG_TRY(gemm_nt(ws.Aloc, D, w->loc_w, D, w->loc_b, ws.Xloc, S, nb * ncols, S, D, 0, st));
+            SG_TRY(norm_rows(ws.Xloc, ws.Xloc, nb * ncols, S, 1e-8f, 0, 0, st));
         }
         // 4. sim_glo
         if (glo_loc) {
             // row 0 of image ii's "region set" <- img_glo[i0 + ii] (the other 35 rows stay zero), then the local-node kernel
-            ITR_CHECK_HIP(hipMemcpy2DAsync(gimg, (size_t)SC_R * D * 4, img_glo + i0 * D, (size_t)D * 4, (size_t)D * 4, (size_t)nb,
+            ITR_CHECK_HIP(hipMemcpy2DAsync(ws.gimg, (size_t)SC_R * D * 4, ws.img_glo + i0 * D, (size_t)D * 4, (size_t)D * 4, (size_t)nb,
                                            hipMemcpyDeviceToDevice, st));
-            SG_TRY(sgraf_loc_fused(Pg, cng, gimg, cap_glo, w->glo_w, w->glo_b, Xglo, nb, NcP / SC_NT, D, st));
+            SG_TRY(sgraf_loc_fused(ws.Pg, ws.cng, ws.gimg, ws.cap_glo, w->glo_w, w->glo_b, ws.Xglo, nb, NcP / SC_NT, D, st));
         } else {
-            hipLaunchKernelGGL(glo_sqdiff_kernel, dim3((unsigned)Nc, (unsigned)nb), dim3(256), 0, st, img_glo + i0 * D, cap_glo, Nc, D, Aglo);
+            hipLaunchKernelGGL(glo_sqdiff_kernel, dim3((unsigned)Nc, (unsigned)nb), dim3(256), 0, st, ws.img_glo + i0 * D, ws.cap_glo, Nc, D, ws.Aglo);
             ITR_CHECK_LAUNCH("sgraf glo_sqdiff");
-            SG_TRY(gemm_nt(Aglo, D, w->glo_w, D, w->glo_b, Xglo, S, nb * Nc, S, D, 0, st));
-            SG_TRY(norm_rows(Xglo, Xglo, nb * Nc, S, 1e-8f, 0, 0, st));
+            SG_TRY(gemm_nt(ws.Aglo, D, w->glo_w, D, w->glo_b, ws.Xglo, S, nb * Nc, S, D, 0, st));
+            SG_TRY(norm_rows(ws.Xglo, ws.Xglo, nb * Nc, S, 1e-8f, 0, 0, st));
         }
         const int64_t npairs = nb * Nc;
         if (module == 0) {
@@ -671,10 +636,10 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
         } else if (fused_sgr) {
             // all the graph steps up to the last step's attention in one workgroup per group of captions; the last step's graph
             // projection of node 0 (the only node read afterwards, Fusionmodule.py:443) for ALL the graphs of the block as one GEMM
-            SG_TRY(sgr_fused_scores(Xloc, Xglo, fused_ws, n_node_groups, Nc, nb, ldg, ncols, vfold, w->sgr_g_b, sgr_step, Yglo,
+            SG_TRY(sgr_fused_scores(ws.Xloc, ws.Xglo, ws.fused_ws, n_node_groups, Nc, nb, ldg, ncols, ws.vfold, w->sgr_g_b, sgr_step, ws.Yglo,
                                     !(flags & ITR_SGRAF_NON_PERSISTENT), st));
-            SG_TRY(gemm_nt(Yglo, S, w->sgr_g_w[sgr_step - 1], S, w->sgr_g_b[sgr_step - 1], Xglo, S, nb * ldg, S, S, 1 /*relu*/, st));
-            hipLaunchKernelGGL(sgr_final_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, Xglo, Nc, S, w->eval_w, w->eval_b,
+            SG_TRY(gemm_nt(ws.Yglo, S, w->sgr_g_w[sgr_step - 1], S, w->sgr_g_b[sgr_step - 1], ws.Xglo, S, nb * ldg, S, S, 1 /*relu*/, st));
+            hipLaunchKernelGGL(sgr_final_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, ws.Xglo, Nc, S, w->eval_w, w->eval_b,
                                npairs, Sout, ldS, i0, ldg);
             ITR_CHECK_LAUNCH("sgraf sgr_final (fused steps)");
         } else {
@@ -682,32 +647,32 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
             ITR_UNSUPPORTED(S % 16 != 0, "itr_sgraf_scores: SGR needs sim_dim %% 16 == 0");
             for (int k = 0; k < sgr_step; ++k) {
                 const int last = (k == sgr_step - 1);
-                if (!last) SG_TRY(gemm_nt(Xloc, S, Wfold[k], S, vfold[k], Qloc, S, nb * ncols, S, S, 0, st));   // last: only node 0 queries
-                SG_TRY(gemm_nt(Xglo, S, Wfold[k], S, vfold[k], Qglo, S, nb * ldg, S, S, 0, st));
+                if (!last) SG_TRY(gemm_nt(ws.Xloc, S, ws.Wfold[k], S, ws.vfold[k], ws.Qloc, S, nb * ncols, S, S, 0, st));   // last: only node 0 queries
+                SG_TRY(gemm_nt(ws.Xglo, S, ws.Wfold[k], S, ws.vfold[k], ws.Qglo, S, nb * ldg, S, S, 0, st));
                 const dim3 pgrid((unsigned)ceil_div(npairs, 4));
                 auto plds = [](int nt) { return (size_t)4 * (nt * 16) * (nt * 16 + 4) * 4; };   // 4 waves x P[NT*16][NT*16+4]
                 if (ntmax == 1) {
-                    hipLaunchKernelGGL(sgr_pair_kernel<1>, pgrid, dim3(256), plds(1), st, pa, Qglo, Qloc, Xglo, Xloc, Yglo, Yloc, npairs, 1, last);
+                    hipLaunchKernelGGL(sgr_pair_kernel<1>, pgrid, dim3(256), plds(1), st, pa, ws.Qglo, ws.Qloc, ws.Xglo, ws.Xloc, ws.Yglo, ws.Yloc, npairs, 1, last);
                 } else {
-                    hipLaunchKernelGGL(sgr_pair_kernel<2>, pgrid, dim3(256), plds(2), st, pa, Qglo, Qloc, Xglo, Xloc, Yglo, Yloc, npairs, 1, last);
+                    hipLaunchKernelGGL(sgr_pair_kernel<2>, pgrid, dim3(256), plds(2), st, pa, ws.Qglo, ws.Qloc, ws.Xglo, ws.Xloc, ws.Yglo, ws.Yloc, npairs, 1, last);
                     if (ntmax > 2) {
                         ITR_CHECK_LAUNCH("sgraf sgr_pair");
-                        hipLaunchKernelGGL(sgr_pair_kernel<4>, pgrid, dim3(256), plds(4), st, pa, Qglo, Qloc, Xglo, Xloc, Yglo, Yloc, npairs, 3, last);
+                        hipLaunchKernelGGL(sgr_pair_kernel<4>, pgrid, dim3(256), plds(4), st, pa, ws.Qglo, ws.Qloc, ws.Xglo, ws.Xloc, ws.Yglo, ws.Yloc, npairs, 3, last);
                     }
                 }
                 ITR_CHECK_LAUNCH("sgraf sgr_pair");
                 // NOTE: a word node is shared by all captions... it is NOT: node rows are per (image, word) and a word
                 // belongs to one caption, so writing Yloc rows per pair is race-free.
-                if (!last) SG_TRY(gemm_nt(Yloc, S, w->sgr_g_w[k], S, w->sgr_g_b[k], Xloc, S, nb * ncols, S, S, 1 /*relu*/, st));
-                SG_TRY(gemm_nt(Yglo, S, w->sgr_g_w[k], S, w->sgr_g_b[k], Xglo, S, nb * ldg, S, S, 1, st));
+                if (!last) SG_TRY(gemm_nt(ws.Yloc, S, w->sgr_g_w[k], S, w->sgr_g_b[k], ws.Xloc, S, nb * ncols, S, S, 1 /*relu*/, st));
+                SG_TRY(gemm_nt(ws.Yglo, S, w->sgr_g_w[k], S, w->sgr_g_b[k], ws.Xglo, S, nb * ldg, S, S, 1, st));
             }
-            hipLaunchKernelGGL(sgr_final_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, Xglo, Nc, S, w->eval_w, w->eval_b,
+            hipLaunchKernelGGL(sgr_final_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, ws.Xglo, Nc, S, w->eval_w, w->eval_b,
                                npairs, Sout, ldS, i0, ldg);
             ITR_CHECK_LAUNCH("sgraf sgr_final");
         }
     }
     // a refused group of a hand-made node-group plan: NaN in its captions' columns (never uninitialised memory; sgr_fused.hip)
-    if (fused_sgr) SG_TRY(sgr_fused_finish(fused_ws, n_node_groups, Nc, sgr_step, Ni, Sout, ldS, st));
+    if (fused_sgr) SG_TRY(sgr_fused_finish(ws.fused_ws, n_node_groups, Nc, sgr_step, Ni, Sout, ldS, st));
 #undef SG_TRY
     return ITR_OK;
 }

@@ -22,6 +22,7 @@
 // stage-2 MFMAs, one barrier mid-way, the next fragments are read behind the second half.  The C++ loop it replaces ran
 // stage 1 after stage 2 and then met a barrier: 127 -> 137 TFLOP/s (stage 1 + 2 flop, SGRAF 1k x 5k).
 #include "scan_common.h"
+#include "itr_internal.h"
 #include <stdlib.h>
 #include <vector>
 
@@ -171,7 +172,6 @@ __global__ __launch_bounds__(256, 2) void sgraf_loc_kernel(LocArgs g) {
     }
 }
 
-int allow_dynamic_lds(const void *kernel, size_t bytes);      // scan_train.hip
 
 int sgraf_loc_fused(const float *P, const float *cn, const float *img, const float *wtiled, const float *W, const float *bias,
                     float *X, int64_t nb, int64_t n_tiles, int D, hipStream_t st) {

@@ -15,12 +15,11 @@
 // image against ALL words of the batch (caption boundaries matter only to the two small softmax / l2norm kernels), and the reductions
 // of the backward pass run along whole axes: d words = sum over b, d regions = sum over t.  The dense layers between these stages are
 // the library's GEMMs (autograd.linear: NT forward / dx, split-row TN for dW); this file is the ragged glue, forward and backward.
-#include "itr_common.h"
+#include "itr_internal.h"
 #include <mutex>
 
 namespace itr {
 
-int allow_dynamic_lds(const void *kernel, size_t bytes);      // scan_train.hip
 
 __device__ __forceinline__ float block_sum_256(float v, float *red4) {       // red4: 4 floats of LDS; all 256 threads call
     v = wave_sum(v);

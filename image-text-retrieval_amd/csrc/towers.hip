@@ -9,28 +9,12 @@
 // prefix (h[0:n_t] x W_hh^T) plus one fused gate kernel (sigmoid / tanh / state update / output
 // write, direction average and last-step gather folded in).
 #include <stdlib.h>
-#include "itr_common.h"
+#include "itr_internal.h"
 #include <mutex>
 #define ITR_SIDE_STREAM_IMPL
 #include "side_stream.h"
-#include <mutex>
 
 namespace itr {
-
-int gemm_nt(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C,
-            int64_t ldc, int64_t M, int64_t N, int64_t K, int act, hipStream_t st);
-// the two directions of a bi-GRU time step in one launch (gemm_f32.hip)
-bool gemm_pair_ok(int64_t lda, int64_t ldb, int64_t K);
-int gemm_nt_pair(const float *A, const float *A2, int64_t lda, const float *B, const float *B2, int64_t ldb, const float *bias, const float *bias2,
-                 float *C, float *C2, int64_t ldc, int64_t M, int64_t N, int64_t K, hipStream_t st);
-int norm_rows(const float *x, float *y, int64_t rows, int dim, float eps, int kind, int take_abs,
-              hipStream_t st);
-// skinny GEMMs of the recurrence when the batch is small (the reference-shaped encode_data path feeds 128 captions at
-// a time): split-K with a deterministic reduction (gemm_f32.hip)
-int gemm_splitk_choice(int64_t M, int64_t N, int64_t K);
-size_t gemm_splitk_scratch_bytes(int64_t M, int64_t N, int splits);
-int gemm_nt_splitk(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int64_t M, int64_t N,
-                   int64_t K, int act, int accumulate, int splits, float *scratch, hipStream_t st);
 
 // x rows are padded with zeros to Ep = E rounded up to 32 columns (300 -> 320) so that the input projection runs on
 // the branch-free GEMM path (K % 32 == 0); the matching zero-padded copy of W_ih is made by pad_cols_kernel.
@@ -166,10 +150,10 @@ __global__ __launch_bounds__(256) void avg2_scalar_kernel(float *__restrict__ ou
 }
 
 // (SideStream / side_stream: side_stream.h)
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct GruWs {
     float *x, *gi, *gh, *h, *out_tmp, *wpad, *skbuf;
+    size_t bytes;
 };
 
 // split-K scratch only for batches that need it (<= 1024 captions: 16 slices x B x 3D floats <= 200 MB)
@@ -178,17 +162,20 @@ static inline size_t gru_splitk_bytes(int64_t B, int D) { return B <= 1024 ? gem
 static inline int pad32(int E) { return (E + 31) / 32 * 32; }
 static inline int64_t pad128(int64_t B) { return (B + 127) / 128 * 128; }
 
-static GruWs carve(void *ws, int64_t n_tok, int64_t B, int E, int D) {
-    char *p = static_cast<char *>(ws);
-    GruWs w;
-    w.x = reinterpret_cast<float *>(p); p += al256((size_t)n_tok * pad32(E) * 4);
-    w.gi = reinterpret_cast<float *>(p); p += al256((size_t)n_tok * 3 * D * 4);
-    w.gh = reinterpret_cast<float *>(p); p += al256((size_t)pad128(B) * 3 * D * 4);      // (rows padded to whole 128-row GEMM tiles: see the recurrence)
-    w.h = reinterpret_cast<float *>(p); p += al256((size_t)pad128(B) * D * 4);
-    w.out_tmp = reinterpret_cast<float *>(p); p += al256((size_t)n_tok * D * 4);
-    w.wpad = reinterpret_cast<float *>(p); p += al256((size_t)3 * D * pad32(E) * 4);
-    w.skbuf = reinterpret_cast<float *>(p); p += al256(gru_splitk_bytes(B, D));
-    return w;
+// One direction's workspace; a bi-GRU's reverse direction has a second one right behind it.
+static GruWs gru_ws(void *ws, int64_t n_tok, int64_t B, int E, int D) {
+    WsCarver c(ws);
+    GruWs t;
+    t.x = c.take<float>((size_t)n_tok * pad32(E) * 4);
+    t.gi = c.take<float>((size_t)n_tok * 3 * D * 4);
+    t.gh = c.take<float>((size_t)pad128(B) * 3 * D * 4);      // (rows padded to whole 128-row GEMM tiles: see the recurrence)
+    t.h = c.take<float>((size_t)pad128(B) * D * 4);
+    t.out_tmp = c.take<float>((size_t)n_tok * D * 4);
+    t.wpad = c.take<float>((size_t)3 * D * pad32(E) * 4);
+    t.skbuf = c.take<float>(gru_splitk_bytes(B, D));
+    c.take(256);
+    t.bytes = c.bytes;
+    return t;
 }
 
 }  // namespace itr
@@ -209,16 +196,9 @@ extern "C" int itr_proj_l2norm(const float *x, const float *W, const float *b, f
     return ITR_OK;
 }
 
-static size_t gru_ws_one(int64_t n_tok, int64_t B, int E, int D) {
-    using itr::al256;
-    return al256((size_t)n_tok * itr::pad32(E) * 4) + al256((size_t)n_tok * 3 * D * 4) + al256((size_t)itr::pad128(B) * 3 * D * 4) +
-           al256((size_t)itr::pad128(B) * D * 4) + al256((size_t)n_tok * D * 4) + al256((size_t)3 * D * itr::pad32(E) * 4) +
-           al256(itr::gru_splitk_bytes(B, D)) + 256;
-}
-
 extern "C" size_t itr_gru_workspace_bytes(int64_t n_tok, int64_t B, int E, int D, int bidirectional) {
     // a bi-GRU runs its two directions side by side (second HIP stream): each needs its own gate pre-activations and state
-    return gru_ws_one(n_tok, B, E, D) * (bidirectional ? 2 : 1);
+    return itr::gru_ws(nullptr, n_tok, B, E, D).bytes * (bidirectional ? 2 : 1);
 }
 
 extern "C" int itr_gru_fwd(const int64_t *tokens, const int64_t *tok_off, const int32_t *len_dev,
@@ -251,7 +231,8 @@ extern "C" int itr_gru_fwd(const int64_t *tokens, const int64_t *tok_off, const 
     }
     ITR_REQUIRE(total == n_tok, "itr_gru_fwd: sum(len) = %lld != n_tok = %lld", (long long)total, (long long)n_tok);
     hipStream_t st = as_stream(stream);
-    GruWs w = carve(workspace, n_tok, B, E, D);
+    GruWs w = gru_ws(workspace, n_tok, B, E, D);
+    const size_t half = w.bytes;      // (the reverse direction's workspace starts here)
     float *seq = out ? out : w.out_tmp;
     const int Lmax = len_host[0];
 
@@ -280,7 +261,7 @@ extern "C" int itr_gru_fwd(const int64_t *tokens, const int64_t *tok_off, const 
 
     GruWs w2 = w;
     if (bi) {
-        w2 = carve(static_cast<char *>(workspace) + gru_ws_one(n_tok, B, E, D), n_tok, B, E, D);
+        w2 = gru_ws(static_cast<char *>(workspace) + half, n_tok, B, E, D);
         w2.x = w.x;                      // the gathered embeddings are shared (read-only)
     }
     // ---- last-state output (VSE++ / VSRN): the forward recurrence without sequence stores; of the backward direction only its first
@@ -299,7 +280,7 @@ extern "C" int itr_gru_fwd(const int64_t *tokens, const int64_t *tok_off, const 
         if (rc != ITR_OK) return rc;
         ITR_CHECK_HIP(hipMemsetAsync(w.h, 0, (size_t)B * D * 4, st));
         if (bi) {      // the backward direction's one step: projection of the B last tokens (the second workspace half's unused x region)
-            float *x_last = reinterpret_cast<float *>(static_cast<char *>(workspace) + gru_ws_one(n_tok, B, E, D));
+            float *x_last = reinterpret_cast<float *>(static_cast<char *>(workspace) + half);
             if (table)
                 hipLaunchKernelGGL(gather_last_rows_tab_kernel, dim3((unsigned)B), dim3(128), 0, st, w.x, tokens, V, tok_off, len_dev, Ep, x_last);
             else
@@ -408,7 +389,7 @@ extern "C" int itr_gru_fwd(const int64_t *tokens, const int64_t *tok_off, const 
     // in the other direction's last round of tiles.  Bit-identical results either way (same fmaf chain per element).
     const bool paired = input_first && splits_h == 1 && D % 4 == 0 && gemm_pair_ok(D, D, D) && want_paired;
     if (paired) {
-        const int64_t dir_stride = (int64_t)(gru_ws_one(n_tok, B, E, D) / 4);
+        const int64_t dir_stride = (int64_t)(half / 4);
         int64_t n_act = B;
         for (int t = 0; t < Lmax; ++t) {
             while (n_act > 0 && len_host[n_act - 1] <= t) --n_act;

@@ -8,7 +8,7 @@
 //   itr_smry_fwd / _bwd              L = softmax(smry_mat, dim=1);  out[b, v, :] = sum_r L[b, r, v] x[b, r, :]   (ImgEncoder.py:386-387)
 //   itr_groupmax_fwd / _bwd          MultiViewMatching: S[i, c] = max_v T[i * k + v, c] with the arg-max view kept
 // All HBM-bound elementwise / short-reduction kernels.
-#include "itr_common.h"
+#include "itr_internal.h"
 
 namespace itr {
 
@@ -225,7 +225,6 @@ __global__ __launch_bounds__(256) void l2norm_mid_bwd_kernel(const float *__rest
 }
 
 // ---- multi-view summarisation: L = softmax over the R regions of smry [B, R, K]; out[b, v, d] = sum_r L[b, r, v] x[b, r, d]
-int allow_dynamic_lds(const void *kernel, size_t bytes);      // scan_train.hip
 constexpr int SM_R = 192, SM_K = 192;    // (SGRAF: K = words of a caption / graph nodes; the longest Flickr30k caption has 82 tokens.  The R x K softmax block is
                                          //  dynamic LDS: 36 KB at 96 x 96, 144 KB at the limit)
 __global__ __launch_bounds__(256) void smry_fwd_kernel(const float *__restrict__ smry, const float *__restrict__ x, float *__restrict__ Lout,

@@ -93,12 +93,17 @@ def _gru_weights(V, E, D, bi, seed):
     return w
 
 
-@pytest.mark.parametrize("bi", [False, True])
-@pytest.mark.parametrize("last", [False, True])
-def test_gru_backward_vs_oracle_autograd(dev, bi, last):
+# every (bi, last) on a small GRU; plus E = 768, D = 1 024 over ~4 000 tokens, where the weight-gradient GEMMs (Q = D and Q = E) need
+# different scratch sizes and the larger one is not the one of the larger Q
+GRU_BWD_CASES = [pytest.param(bi, last, False, id="%s-%s" % (last, bi)) for bi in (False, True) for last in (False, True)]
+GRU_BWD_CASES.append(pytest.param(False, False, True, id="E768-D1024"))
+
+
+@pytest.mark.parametrize("bi,last,wide", GRU_BWD_CASES)
+def test_gru_backward_vs_oracle_autograd(dev, bi, last, wide):
     rng = np.random.RandomState(3)
-    V, E, D, B = 40, 12, 32, 9
-    lens = sorted([int(x) for x in rng.randint(1, 8, size=B)], reverse=True)
+    V, E, D, B = (1000, 768, 1024, 100) if wide else (40, 12, 32, 9)
+    lens = sorted([int(x) for x in (rng.randint(30, 51, size=B) if wide else rng.randint(1, 8, size=B))], reverse=True)
     ids = torch.zeros(B, max(lens), dtype=torch.long)
     for b, l in enumerate(lens):
         ids[b, :l] = T(rng.randint(0, V, size=l))
@@ -129,7 +134,9 @@ def test_gru_backward_vs_oracle_autograd(dev, bi, last):
     want = cap if last else cap[mask.cpu()[:, :max(lens)]]
     assert md(out, want) <= 2e-6
     for k in w:
-        assert md(wd[k].grad, wl[k].grad) <= 5e-6, k
+        # wide: the gradients are sums over ~4 000 tokens and reach 10-250; the fp32 oracle alone is off by up to 4e-7 of the largest
+        tol = 2e-6 * max(1.0, float(wl[k].grad.abs().max())) if wide else 5e-6
+        assert md(wd[k].grad, wl[k].grad) <= tol, k
 
 
 NORMS = ['clipped_l2norm', 'l2norm', 'no_norm', 'clipped', 'softmax', 'l1norm', 'clipped_l1norm']
