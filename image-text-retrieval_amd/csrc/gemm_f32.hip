@@ -445,7 +445,7 @@ int gemm_nt_splitk_partials(const float *A, int64_t lda, const float *B, int64_t
     const size_t fit = scratch_bytes / gemm_splitk_scratch_bytes(M, N, 1);      // whole M x N slices
     // M <= 128 rows (a training batch's recurrence): 16-column strips over all rows instead of one 128-row tile per 128 columns
     // (gemm_skinny.hip), up to 16 slices of M x N as the scratch holds; the consumer adds whatever number of slices comes back
-    if (splits > 1 && fit >= 1 && !ITR_EXP_ENV("ITR_GEMM_NO_SKINNY") && gemm_skinny_ok(A, lda, B, ldb, M, N, K))
+    if (splits > 1 && fit >= 1 && gemm_skinny_ok(A, lda, B, ldb, M, N, K))
         return gemm_skinny_partials(A, lda, B, ldb, M, N, K, fit < 16 ? (int)fit : 16, scratch, n_slices, st);
     const int64_t ksplit = ceil_div(ceil_div(K, (int64_t)(splits > 1 ? splits : 1)), (int64_t)BK) * BK;
     const int ns = (int)ceil_div(K, ksplit);

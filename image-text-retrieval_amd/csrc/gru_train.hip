@@ -15,7 +15,6 @@
 // then, over ALL tokens at once (MFMA GEMMs on transposed operands):
 //     dW_hh = dgh^T H_prev    db_hh = colsum(dgh)    dW_ih = dgi^T X    db_ih = colsum(dgi)    dX (+)= dgi W_ih
 // and dE[token] += dX (atomic scatter; the only non-deterministic summation order of the step).
-#include <stdlib.h>
 #include "itr_internal.h"
 #include "side_stream.h"
 
@@ -222,7 +221,6 @@ extern "C" int itr_gru_fwd_train(const int64_t *tokens, const int64_t *tok_off, 
     hipStream_t st = as_stream(stream);
     GruTrainWs w = gru_train_ws(workspace, n_tok, B, E, D);
     const int splits_h = gemm_splitk_choice(B, 3 * D, D);
-    const bool fuse = ITR_EXP_ENV("ITR_GRU_REDUCE_KERNEL") == nullptr;   // tools/ A/B switch: separate reduction kernel
     const int Lmax = len_host[0];
     ITR_CHECK_HIP(hipMemsetAsync(w.bad, 0, sizeof(int), st));
     hipLaunchKernelGGL(embed_gather_train_kernel, dim3((unsigned)n_tok), dim3(128), 0, st, tokens, n_tok, embed, V, E, w.x, w.bad);
@@ -245,7 +243,7 @@ extern "C" int itr_gru_fwd_train(const int64_t *tokens, const int64_t *tok_off, 
         for (int t = 0; t < Lmax; ++t) {
             while (n_act > 0 && len_host[n_act - 1] <= t) --n_act;
             int ns = 0;
-            if (splits_h > 1 && fuse) rc2 = gemm_nt_splitk_partials(d.h, D, wh, D, n_act, 3 * D, D, splits_h, d.skbuf, w.sk_bytes, &ns, sd);
+            if (splits_h > 1) rc2 = gemm_nt_splitk_partials(d.h, D, wh, D, n_act, 3 * D, D, splits_h, d.skbuf, w.sk_bytes, &ns, sd);
             else rc2 = gemm_nt_splitk(d.h, D, wh, D, bh, d.gh, 3 * D, n_act, 3 * D, D, 0, 0, splits_h, d.skbuf, sd);
             if (rc2 != ITR_OK) return rc2;
             // the reverse direction writes its own output plane; the average with the forward direction follows the join
@@ -284,7 +282,6 @@ extern "C" int itr_gru_bwd(const int64_t *tokens, const int64_t *tok_off, const 
     hipStream_t st = as_stream(stream);
     GruTrainWs w = gru_train_ws(workspace, n_tok, B, E, D);
     const int splits_c = gemm_splitk_choice(B, D, 3 * D);
-    const bool fuse = ITR_EXP_ENV("ITR_GRU_REDUCE_KERNEL") == nullptr;
     const int Lmax = len_host[0];
 
     ITR_CHECK_HIP(hipMemsetAsync(w.bad, 0, sizeof(int), st));
@@ -318,7 +315,7 @@ extern "C" int itr_gru_bwd(const int64_t *tokens, const int64_t *tok_off, const 
             ITR_CHECK_LAUNCH("gru_gate_bwd");
             ns_pending = 0;
             if (t > 0) {
-                if (splits_c > 1 && fuse) {   // slices of dgh W_hh stay in scratch: the next gate kernel adds them to carry
+                if (splits_c > 1) {   // slices of dgh W_hh stay in scratch: the next gate kernel adds them to carry
                     GB_TRY(gemm_nt_splitk_partials(d.dgh_step, 3 * D, d.whhT, 3 * D, n_act, D, 3 * D, splits_c, d.skbuf, w.sk_bytes, &ns_pending, sd));
                     prev_n = n_act;
                 } else {

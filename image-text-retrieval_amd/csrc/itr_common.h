@@ -7,17 +7,7 @@
 
 #include "../../include/itr_hip.h"
 
-// Experiment switches (ablations, phase traces, scheduling variants that lost in earlier rounds) exist ONLY in builds made with
-// -DITR_EXPERIMENT (tools/ab_build.sh): there ITR_EXP_ENV("NAME") is getenv("NAME").  In the shipped library it is a null constant --
-// the library reads NO environment variable (re-entrant, no global mutable state beyond the error string), the switch
-// names do not appear in the binary, and the compiler folds the alternative paths away.  Variants the tests cross-check against
-// (the step-by-step SGR chain, the tile GEMM, the paired GRU launch order ...) are explicit ARGUMENTS of the ABI instead.
-#ifdef ITR_EXPERIMENT
-#include <stdlib.h>
-#define ITR_EXP_ENV(name) ::getenv(name)
-#else
-#define ITR_EXP_ENV(name) (static_cast<const char *>(nullptr))
-#endif
+// The library reads no environment variable: every variant the tests cross-check against is an argument of the ABI.
 
 namespace itr {
 

@@ -57,13 +57,8 @@ __device__ __forceinline__ unsigned long long rank_key(float e, unsigned idx) { 
 //       atomicMax per row (other column blocks -- and nobody else -- add to the same row).
 // RF_U rows are requested before the first is consumed (the old kernels had one 16-byte load per lane in flight and relied on
 // occupancy alone: they were latency-bound, not ALU- or HBM-bound).
-#ifndef ITR_RF_U
-#define ITR_RF_U 4
-#endif
-#ifndef ITR_RF_WAVES              // waves per SIMD the register allocation must admit
-#define ITR_RF_WAVES 4
-#endif
-constexpr int RF_U = ITR_RF_U;    // rows in the register ring of a lane (RF_U - 1 in flight at all times); divides 64
+constexpr int RF_U = 4;           // rows in the register ring of a lane (RF_U - 1 in flight at all times); divides 64
+constexpr int RF_WAVES = 4;       // waves per SIMD the register allocation must admit
 // rows per workgroup: a multiple of 64 chosen per launch (itr_rank_counts) so that the grid fits the resident slots of the chip in ONE
 // round where it can (1 000 workgroups of 128 rows on 768 slots were two rounds for 1.3 rounds of work)
 constexpr int RF_COLS = RANK_THREADS * 4;
@@ -235,7 +230,7 @@ __device__ __forceinline__ void rank_tile(const float *__restrict__ S, int64_t l
         }
 }
 
-__global__ __launch_bounds__(RANK_THREADS, ITR_RF_WAVES) void rank_fused_kernel(const float *__restrict__ S, int64_t ldS, int64_t row0, int64_t nrows,
+__global__ __launch_bounds__(RANK_THREADS, RF_WAVES) void rank_fused_kernel(const float *__restrict__ S, int64_t ldS, int64_t row0, int64_t nrows,
                                                                   int64_t Nc, int im_div, const float *__restrict__ s_gt,
                                                                   const unsigned long long *__restrict__ row_gkey,
                                                                   int32_t *__restrict__ i2t_cnt, unsigned long long *__restrict__ row_best,

@@ -18,12 +18,8 @@
     const int nk = g.D / SC_BK;  // D % 32 == 0 is checked on the host
     const unsigned rowbytes = (unsigned)g.D * 4u;
     const int64_t n_img_rows = g.Ni * SC_R;
-    // (debug & 32, tools/scan_traffic_exp.py: EVERY workgroup reads the operands of the first 16 images x 4 column tiles -- 3.4 MB,
-    // resident in each XCD's L2 -- instead of its own: same instruction stream and matrix work, no fabric traffic; the scores are
-    // garbage.  An experiment on whether the 1.2 TB of fabric traffic per launch costs time or clock: DESIGN.md 4.3.)
-    const int64_t img0_ld = (g.debug & 32) ? (img0 & 15) : img0, ct_ld = (g.debug & 32) ? (ct & 3) : ct;
-    const char *abase = reinterpret_cast<const char *>(g.img) + img0_ld * SC_R * (int64_t)rowbytes;
-    const char *bbase = reinterpret_cast<const char *>(g.wtiled) + ct_ld * SC_NT * (int64_t)rowbytes;
+    const char *abase = reinterpret_cast<const char *>(g.img) + img0 * SC_R * (int64_t)rowbytes;
+    const char *bbase = reinterpret_cast<const char *>(g.wtiled) + ct * SC_NT * (int64_t)rowbytes;
     const int64_t bpass = 32 * (int64_t)rowbytes;    // B pass 1 = B pass 0 + 32 rows: a second scalar base, no second VGPR
     unsigned va0, va1, va2, va3, va4, vb0;            // per-lane global byte offsets
     unsigned la0, la4;                                // per-lane LDS byte addresses (buffer 0).  Every other pass is la0 + an

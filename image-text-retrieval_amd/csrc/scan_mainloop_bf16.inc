@@ -20,8 +20,8 @@
 //   {g ^ p0, g ^ 1 ^ p1, g ^ 1 ^ p2, g ^ p3} must differ: p = (0, 3, 2, 1) does it (the round-3 map p = (0, 1, 2, 3) put rows q + 4 on rows
 //   q and rows q + 8 on rows q + 12: 2-way on every read).  Stores: the eight lanes of a ds_write_b128 group write one row's 64 B of
 //   plane 0 and of plane 1; the planes are a multiple of 128 B apart, so without the r ^ 1 both landed on the same 16 banks.
-//   Wave tiling: with 16-cycle MFMAs the loop is bound by LDS bandwidth, not by the matrix pipe (tools/scan_ablate2.py bf16x3:
-//   the same time with the MFMAs removed), so the waves are tiled 2 x 2 instead of 1 x 4: wave = (row half rh, column pair cp)
+//   Wave tiling: with 16-cycle MFMAs the loop is bound by LDS bandwidth, not by the matrix pipe (measured: the
+//   same time with the MFMAs removed), so the waves are tiled 2 x 2 instead of 1 x 4: wave = (row half rh, column pair cp)
 //   owns row tiles 4 rh .. 4 rh + 4 (tile 4 is computed by both halves -- 10 % more MFMAs, no divergence) x column tiles
 //   2 cp, 2 cp + 1: 14 fragment reads per wave and chunk instead of 20.  Only the park below knows the tiling; the epilogue
 //   reads the parked block.
@@ -108,12 +108,12 @@
 #define SC_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0);
 #define SC_CHUNK(P, CUR, NXT, KC, BHC, BHN)                                                        \
     {                                                                                              \
-        if constexpr (!(PREC & 4)) SC_VMWAIT(P, 7)                                                 \
+        SC_VMWAIT(P, 7)                                                                            \
         SC_LSTORE(P, NXT)                                                                          \
-        if constexpr (!(PREC & 4)) SC_GLOAD(P, ((KC) + 3 < klast ? (KC) + 3 : klast))              \
+        SC_GLOAD(P, ((KC) + 3 < klast ? (KC) + 3 : klast))                                         \
         _Pragma("unroll") for (int i = 0; i < WR; ++i)                                             \
             fal[i] = SC_LDS4(ra_l + (CUR) * STAGE_BYTES + i * 1024);                               \
-        if constexpr (!(PREC & 8)) { SC_MM(fah, BHC, acc) if constexpr (DUAL) { SC_MM(fah, fbl, acx) } else { SC_MM(fah, fbl, acc) } }                             \
+        SC_MM(fah, BHC, acc) if constexpr (DUAL) { SC_MM(fah, fbl, acx) } else { SC_MM(fah, fbl, acc) }                           \
         _Pragma("unroll") for (int i_ = 0; i_ < 7; ++i_) { SC_SGB(0x008, 1) SC_SGB(0x200, 1) }     \
         _Pragma("unroll") for (int i_ = 0; i_ < 5; ++i_) { SC_SGB(0x008, 1) SC_SGB(0x100, 1) }     \
         SC_SGB(0x008, 8)                                                                           \
@@ -124,7 +124,7 @@
             BHN[j] = SC_LDS4(rb_h + (NXT) * STAGE_BYTES + j * 1024);                               \
             fbl[j] = SC_LDS4(rb_l + (NXT) * STAGE_BYTES + j * 1024);                               \
         }                                                                                          \
-        if constexpr (!(PREC & 8)) { if constexpr (DUAL) { SC_MM(fal, BHC, acx) } else { SC_MM(fal, BHC, acc) } }                                             \
+        if constexpr (DUAL) { SC_MM(fal, BHC, acx) } else { SC_MM(fal, BHC, acc) }                                                 \
         _Pragma("unroll") for (int i_ = 0; i_ < 9; ++i_) { SC_SGB(0x008, 1) SC_SGB(0x100, 1) }     \
         SC_SGB(0x008, 1)                                                                           \
         if ((KC) >= klast) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   /* last chunk: see the drain note below */ \

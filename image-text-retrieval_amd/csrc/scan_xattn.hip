@@ -27,7 +27,6 @@
 // lds[plane][row ^ plane]; see gemm_f32.hip for the bank-conflict argument (the 16x16x4 MFMA
 // lane groups need plane = 4q + (lane >> 4) so both planes of a ds_read_b128 lane group share
 // bits [3:2] of the XOR).
-#include <stdlib.h>
 #include <type_traits>
 #include <vector>
 
@@ -58,8 +57,7 @@ struct ScanArgs {
     float *emit_p;    // [Ni, n_tiles*64, 36] normalised attention weights (SGRAF: SCAN_attention), or null
     float *emit_cn;   // [Ni, n_tiles*64]     1 / (||ctx|| + eps)
     int tpw;    // tiles per workgroup (see the work mapping in the kernel)
-    int debug;  // ablation switches for tools/scan_ablate.py (env ITR_SCAN_DEBUG); 0 in production
-    unsigned long long *dbg_cycles;  // [8] phase cycle sums (debug & 16), normally null
+    unsigned long long *dbg_cycles;  // [8] phase cycle sums (itr_debug_scan_clock_probe), normally null
 };
 
 struct ScanSmem {
@@ -144,7 +142,7 @@ using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
 using f16x8_t = __attribute__((ext_vector_type(8))) _Float16;
 
 // PREC 0: exact fp32 main loop (scan_mainloop.inc).  PREC 1: split-bf16 "bf16x3", PREC 3: split-fp16 "fp16x3" main loop
-// (scan_mainloop_bf16.inc; opt-in, reported separately -- STUDY_SPLIT_PRECISION.md); bits 2 / 3: ablation builds.  The epilogue is shared.
+// (scan_mainloop_bf16.inc; opt-in, reported separately -- STUDY_SPLIT_PRECISION.md).  The epilogue is shared.
 // XA: the attention direction as a compile-time constant for the exact fp32 build (0 = t2i, 1 = i2t: two kernels, so the i2t epilogue's
 // registers and scalar spills do not weigh on the t2i kernel -- adding 60 lines to the i2t branch cost the t2i kernel 0.3 % while both
 // lived in one function); -1 = g.mode at run time (the study variants).
@@ -199,10 +197,6 @@ __device__ __forceinline__ void scan_xattn_body(const ScanArgs &g) {
     const int norm = g.norm;
     const float ls = g.lambda_softmax;
     const int ncap = sm.meta.ncap;
-    if (g.debug & 1) {  // ablation: no epilogue
-        if (tid < SC_IMGS && img0 + tid < g.Ni) g.S[(img0 + tid) * g.ldS + sm.meta.cap_id[0]] = sm.arawt[0][tid * SC_R];
-        continue;
-    }
 #define AT(row, col) sm.arawt[col][row]
 
     if (mode == 0) {
@@ -384,13 +378,8 @@ __device__ __forceinline__ void scan_xattn_body(const ScanArgs &g) {
                         tail = fmaf(e2[j], tacc[2][nt][j], tail);
                     }
                     part += (fg == 0) ? tail : 0.f;
-#ifdef ITR_SCAN_SHFL_LDS            // A/B build: the round-3 form (two LDS-crossbar round trips per column tile)
-                    part += __shfl_xor(part, 16, 64);
-                    part += __shfl_xor(part, 32, 64);
-#else
                     part = xor16_add(part);       // (bit-identical to the shuffles: see scan_common.h)
                     part = xor32_add(part);
-#endif
                     qn[nt] = part;
                 }
                 // this lane's own column is w = fg*16 + fi -> n-tile fg
@@ -1018,7 +1007,7 @@ namespace itr {
 static int scan_scores_impl2(const float *img, int64_t n_tiles, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D,
                              int mode, int norm, int agg, float lambda_softmax, float lambda_lse, float *S, int64_t ldS,
                              void *workspace, size_t workspace_bytes, float *emit_p, float *emit_cn, int64_t img_index0,
-                             int64_t img_count, void *bf16_ws, int f16, itr_stream_t stream, int debug_bits = 0);
+                             int64_t img_count, void *bf16_ws, int f16, itr_stream_t stream, bool clock_probe = false);
 
 int scan_scores_impl(const float *img, int64_t n_tiles, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D,
                      int mode, int norm, int agg, float lambda_softmax, float lambda_lse, float *S, int64_t ldS,
@@ -1042,7 +1031,7 @@ static ScanBf16Ws scan_bf16_ws(void *base, int64_t Ni, int R, int64_t n_tiles, i
 static int scan_scores_impl2(const float *img, int64_t n_tiles, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D,
                              int mode, int norm, int agg, float lambda_softmax, float lambda_lse, float *S, int64_t ldS,
                              void *workspace, size_t workspace_bytes, float *emit_p, float *emit_cn, int64_t img_index0,
-                             int64_t img_count, void *bf16_ws, int f16, itr_stream_t stream, int debug_bits) {
+                             int64_t img_count, void *bf16_ws, int f16, itr_stream_t stream, bool clock_probe) {
     ITR_REQUIRE(img && S && workspace, "itr_scan_xattn_scores: null pointer");
     ITR_REQUIRE(Ni >= 0 && Nc >= 0 && n_rows >= 0 && n_tiles >= 0 && ldS >= Nc, "itr_scan_xattn_scores: bad shape");
     if (mode != 0 && mode != 1) { set_error("unknown cross_attn mode %d", mode); return ITR_ERR_BADARG; }
@@ -1072,9 +1061,7 @@ static int scan_scores_impl2(const float *img, int64_t n_tiles, int64_t Ni, int6
         Ni = img_count;
         if (Ni == 0) return ITR_OK;
     }
-    a.debug = debug_bits;      // 0, or 16 from itr_debug_scan_clock_probe; the ablation bits exist in experiment builds only
-    if (const char *dbg = ITR_EXP_ENV("ITR_SCAN_DEBUG")) a.debug = atoi(dbg);
-    if (a.debug & 16) {   // phase timing: the caller reads the 8 counters placed at the start of S (S is garbage then)
+    if (clock_probe) {   // phase timing: the caller reads the 8 counters placed at the start of S (S is garbage then)
         a.dbg_cycles = reinterpret_cast<unsigned long long *>(S);
         ITR_CHECK_HIP(hipMemsetAsync(S, 0, 64, st));
         a.S = S + 16;
@@ -1090,12 +1077,10 @@ static int scan_scores_impl2(const float *img, int64_t n_tiles, int64_t Ni, int6
         if (rc == ITR_OK) rc = allow_dynamic_lds(reinterpret_cast<const void *>(scan_xattn_kernel<1>), 160 * 1024);
         if (rc != ITR_OK) return rc;
     }
-    size_t lds = sizeof(ScanSmem);
-    if (const char *ex = ITR_EXP_ENV("ITR_SCAN_LDS_EXTRA")) lds += (size_t)atoi(ex);   // occupancy experiments only
-    // tiles per workgroup (ITR_SCAN_TPW overrides, tools/scan_ablate2.py).  Measured at 1k x 5k: 37.13 / 36.89 / 36.94 / 36.85 ms
-    // for 1 / 2 / 4 / 8 -- the launch gaps of one-tile workgroups are already covered by the co-resident workgroup.
+    const size_t lds = sizeof(ScanSmem);
+    // tiles per workgroup.  Measured at 1k x 5k: 37.13 / 36.89 / 36.94 / 36.85 ms for 1 / 2 / 4 / 8 -- the launch gaps of
+    // one-tile workgroups are already covered by the co-resident workgroup.
     a.tpw = 2;
-    if (const char *te = ITR_EXP_ENV("ITR_SCAN_TPW")) a.tpw = atoi(te) > 0 ? atoi(te) : 1;
     const int64_t grid = ceil_div(ceil_div(PI * PJ, 8), (int64_t)a.tpw) * 64 * 8;
     if (bf16_ws) {
         ITR_UNSUPPORTED((uint64_t)Ni * R * D * 4 >= (1ull << 32) || (uint64_t)SC_NT * D * 4 >= (1ull << 32),
@@ -1113,15 +1098,7 @@ static int scan_scores_impl2(const float *img, int64_t n_tiles, int64_t Ni, int6
         ITR_CHECK_LAUNCH("scan split");
         a.img_bf = img_bf;
         a.wt_bf = wt_bf;
-        // ablation builds of the main loop (tools/scan_ablate2.py bf16x3): 5 = no global loads, 9 = no MFMAs -- results are garbage
-        const int abl = ITR_EXP_ENV("ITR_SCAN_BF16_ABLATE") ? atoi(ITR_EXP_ENV("ITR_SCAN_BF16_ABLATE")) : 0;
-        if (abl == 5) {
-            ITR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_xattn_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            hipLaunchKernelGGL(scan_xattn_kernel<5>, dim3((unsigned)grid), dim3(SC_THREADS), lds, st, a);
-        } else if (abl == 9) {
-            ITR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_xattn_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            hipLaunchKernelGGL(scan_xattn_kernel<9>, dim3((unsigned)grid), dim3(SC_THREADS), lds, st, a);
-        } else if (f16) {
+        if (f16) {
             {
                 const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(scan_xattn_kernel<3>), 160 * 1024);
                 if (rc != ITR_OK) return rc;
@@ -1171,17 +1148,5 @@ extern "C" int itr_debug_scan_clock_probe(const float *img, int64_t n_tiles, int
                                           void *workspace, size_t workspace_bytes, itr_stream_t stream) {
     ITR_REQUIRE(ld_scratch >= Nc + 64, "itr_debug_scan_clock_probe: scratch rows must hold Nc + 64 floats");
     return itr::scan_scores_impl2(img, n_tiles, Ni, Nc, n_rows, R, D, mode, norm, agg, lambda_softmax, lambda_lse, scratch, ld_scratch, workspace,
-                                  workspace_bytes, nullptr, nullptr, 0, -1, nullptr, 0, stream, 16);
-}
-
-// Diagnostics for tools/: resident workgroups per CU of the SCAN kernel as the runtime sees it.
-extern "C" int itr_debug_scan_occupancy(int *blocks_per_cu, int *lds_bytes) {
-    using namespace itr;
-    ITR_REQUIRE(blocks_per_cu && lds_bytes, "itr_debug_scan_occupancy: null pointer");
-    ITR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_xattn_kernel<0, 0>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(ScanSmem)));
-    ITR_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void *>(scan_xattn_kernel<0, 0>),
-                                                               SC_THREADS, sizeof(ScanSmem)));
-    *lds_bytes = (int)sizeof(ScanSmem);
-    return ITR_OK;
+                                  workspace_bytes, nullptr, nullptr, 0, -1, nullptr, 0, stream, true);
 }

@@ -36,7 +36,6 @@
 #include "itr_internal.h"
 #include "pack_plan.h"
 #include <string.h>
-#include <stdlib.h>
 #include <vector>
 
 namespace itr {
@@ -45,17 +44,9 @@ namespace itr {
 // (lanes fi = 0..15 of one quarter-wave) start in 16 distinct slots mod 16, and the four rows 4 fq + r of the value gathers of P2
 // (ds_read_b32, 4 x 260 floats apart = 16 banks) no longer pair up on the same banks as they did at 264 (4 x 264 = 32 banks: the
 // 2-way conflicts of round 3's PMC).  Same-box A/B: 723.7 -> 721.2 ms at 1k x 5k (268: 722.6).
-#ifndef ITR_SF_LNR          // rows per pass / k per weight batch of the last step's VALU projection in the one-per-CU kernel
-#define ITR_SF_LNR 8
-#endif
-#ifndef ITR_SF_LKB
-#define ITR_SF_LKB 8
-#endif
-#ifndef ITR_SF_LD
-#define ITR_SF_LD 260
-#endif
-constexpr int SF_ROWS = 64, SF_S = 256, SF_LD = ITR_SF_LD, SF_MAXCAP = 16, SF_MAXUNIT = 24, SF_THREADS = 512, SF_WAVES = 8;
+constexpr int SF_ROWS = 64, SF_S = 256, SF_LD = 260, SF_MAXCAP = 16, SF_MAXUNIT = 24, SF_THREADS = 512, SF_WAVES = 8;
 constexpr int SF_SMALL = 32;             // node rows of the small class of groups (two workgroups per CU)
+constexpr int SF_LNR = 8, SF_LKB = 8;    // rows per pass / k per weight batch of the last step's VALU projection in the one-per-CU kernel
 
 // One record per group of captions (built on the device from the host's bin plan: sgr_group_meta_kernel).
 struct alignas(16) SgrGroupMeta {
@@ -199,7 +190,6 @@ struct SgrFusedArgs {
     int steps;
     float *y0;                           // [nb][Nc][256]: y of node 0 after the last step's attention (the last graph projection and the score
                                          // run as ONE GEMM over all the graphs of the image block afterwards: sgraf.hip)
-    unsigned long long *trace;           // debug (ITR_SGR_TRACE): [grid][20] = hardware id, group shape, s_memtime at entry / after the load / after every phase
 };
 
 #define SF_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -235,13 +225,8 @@ __device__ __forceinline__ void sf_kblock(unsigned baddr, const float4 *const (&
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (KS < 15) {
-#ifdef SF_EXP_SAME_BLOCK      // timing experiment (tools/ab_build.sh): every k-block re-reads the weights of block 0 (L1 hits; results are garbage)
-        SF_GLOAD(n0, wp[0][0], 0);
-        SF_GLOAD(n1, wp[1][0], 0);
-#else
         SF_GLOAD(n0, wp[0][(KS + 1) / 4], ((KS + 1) % 4) * 1024);
         SF_GLOAD(n1, wp[1][(KS + 1) / 4], ((KS + 1) % 4) * 1024);
-#endif
         SF_LREAD(nb[0], baddr, 64 * (KS + 1));
         if constexpr (NG > 1) SF_LREAD(nb[1], baddr, 16 * SF_LD * 4 + 64 * (KS + 1));
         if constexpr (NG > 2) SF_LREAD(nb[2], baddr, 2 * 16 * SF_LD * 4 + 64 * (KS + 1));
@@ -659,11 +644,8 @@ __device__ __forceinline__ void sf_last_attend_n(const float *__restrict__ xb, c
     const int ntc = (m.nn[ci] + 15) >> 4;
     if constexpr (ROWS > SF_SMALL) {
         switch (ntc) {
-#ifndef ITR_SF_UNR
-#define ITR_SF_UNR 4
-#endif
-            case 1: sf_last_attend<1, ITR_SF_UNR>(xb, qy, m, ci, lane, yout); break;
-            case 2: sf_last_attend<2, ITR_SF_UNR>(xb, qy, m, ci, lane, yout); break;
+            case 1: sf_last_attend<1, 4>(xb, qy, m, ci, lane, yout); break;
+            case 2: sf_last_attend<2, 4>(xb, qy, m, ci, lane, yout); break;
             case 3: sf_last_attend<3, 2>(xb, qy, m, ci, lane, yout); break;
             default: sf_last_attend<4, 2>(xb, qy, m, ci, lane, yout); break;
         }
@@ -719,10 +701,6 @@ __global__ __launch_bounds__(SF_THREADS, 2 * WG_PER_CU) void sgr_fused_kernel(Sg
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if ((int64_t)blockIdx.x >= (int64_t)g.gcount[0] * g.nb) return;      // (the grid is sized for all the groups of the call)
     const int64_t grp = g.glist[blockIdx.x / g.nb], ii = blockIdx.x % g.nb;      // consecutive workgroups: one group, the images of the block
-    int nstamp = 0;
-    // (straight to memory: a local array indexed by a run-time count would live in scratch, inside loops with hand-counted asm loads)
-#define SF_STAMP() { if (g.trace && tid == 0 && nstamp < 16) g.trace[(size_t)blockIdx.x * 20 + 2 + nstamp++] = __builtin_amdgcn_s_memtime(); }
-    SF_STAMP()
     if (tid < (int)(sizeof(SgrGroupMeta) / 4)) reinterpret_cast<int32_t *>(&m)[tid] = reinterpret_cast<const int32_t *>(g.meta + grp)[tid];
     __syncthreads();
     const int ncap = m.ncap, nrows = m.nrows;
@@ -752,12 +730,10 @@ __global__ __launch_bounds__(SF_THREADS, 2 * WG_PER_CU) void sgr_fused_kernel(Sg
             *reinterpret_cast<float4 *>(xb + (wave + SF_WAVES * k) * SF_LD + 4 * lane) = v[k];
     }
     __syncthreads();
-    SF_STAMP()
     const int ng_all = (nrows + 15) >> 4;
     for (int k = 0; k + 1 < g.steps; ++k) {
         sf_project_n<false, ROWS>(ng_all, xb_lds, qy, g.wq[k], g.vq[k], wave, lane, fa0, fa1, g.wg[k]);
         __syncthreads();
-        SF_STAMP()
         // P2.  Units are sorted by size; unit u goes to wave (u & 7) for u & 7 < 4 and to wave 11 - (u & 7) otherwise (a snake
         // over the four SIMDs: waves w and w + 4 share one, and share its matrix pipe).
         const int nu = m.nunit;
@@ -769,7 +745,6 @@ __global__ __launch_bounds__(SF_THREADS, 2 * WG_PER_CU) void sgr_fused_kernel(Sg
             sf_attend_e_n<ROWS>((m.nn[ci] + 15) >> 4, xb_lds, qy_lds, m, ci, tile, lane, pt);
         }
         __syncthreads();
-        SF_STAMP()
         // tasks = unit x feature half, task t -> wave t & 7 (units are sorted by size: waves w and w + 4, which share a SIMD, get the
         // halves of units two places apart)
         for (int t = wave; t < 2 * nu; t += SF_WAVES) {
@@ -779,39 +754,24 @@ __global__ __launch_bounds__(SF_THREADS, 2 * WG_PER_CU) void sgr_fused_kernel(Sg
             sf_attend_y_n<ROWS>((m.nn[ci] + 15) >> 4, xb_lds, qy, m, ci, tile, dq, lane, pt);
         }
         __syncthreads();
-        SF_STAMP()
         sf_project_n<true, ROWS>(ng_all, qy_lds, xb, g.wg[k], g.bg[k], wave, lane, fa0, fa1, g.wq[k + 2 < g.steps ? k + 1 : 0]);
         __syncthreads();
-        SF_STAMP()
     }
     // ---- the last step: node 0 of every graph only, on the vector ALU (see sf_last_project)
-    constexpr int LNR = ROWS > SF_SMALL ? ITR_SF_LNR : 4, LKB = ROWS > SF_SMALL ? ITR_SF_LKB : 4;
+    constexpr int LNR = ROWS > SF_SMALL ? SF_LNR : 4, LKB = ROWS > SF_SMALL ? SF_LKB : 4;
     float4 lw[LKB];
     sf_last_weights0<LKB>(g.wqT_last, wave, lane, lw);
     sf_last_project<LNR, LKB>(xb, qy, g.wqT_last, g.vq[g.steps - 1], ncap, wave, lane, lw);
     __syncthreads();
-    SF_STAMP()
     // y of node 0 -> memory; X'_0 = relu(W_g y + b) and sigmoid(sim_eval_w . x_0 + b) (Fusionmodule.py:443-444) run as one GEMM + one
     // small kernel over ALL the graphs of the image block (sgraf.hip): there the weight is read once per 128 rows, here it was
     // streamed through the CU once per item for 2-5 live rows
     for (int ci = wave; ci < ncap; ci += SF_WAVES)
         sf_last_attend_n<ROWS>(xb, qy, m, ci, lane, g.y0 + (ii * g.Nc + m.cap_id[ci]) * SF_S);
-    SF_STAMP()
-    SF_STAMP()
-    SF_STAMP()
-    if (g.trace && tid == 0) {
-        SF_STAMP()
-        const unsigned hw = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
-        const unsigned xcc = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11));
-        unsigned long long *t = g.trace + (size_t)blockIdx.x * 20;
-        t[0] = ((unsigned long long)xcc << 32) | hw;
-        t[1] = ((unsigned long long)nrows << 32) | (unsigned)(m.nunit << 8) | (unsigned)ncap;
-    }
-#undef SF_STAMP
 }
 
-// Persistent form (default; ITR_SGR_PERSISTENT=0 launches one workgroup per (image, group) instead): one workgroup per CU walks
-// the (group, image) list with stride gridDim.x.  What it buys is the 64 KB of node rows of the NEXT item, requested when the last
+// Persistent form (default; the itr_sgraf_scores flag ITR_SGRAF_NON_PERSISTENT launches one workgroup per (image, group) instead):
+// one workgroup per CU walks the (group, image) list with stride gridDim.x.  What it buys is the 64 KB of node rows of the NEXT item, requested when the last
 // step's attention starts (11 k cycles with nothing else on the vector-memory counter: the k-blocks of the last projection wait
 // with vmcnt(0), and loads complete in order) into 8 registers per lane, and stored into the X buffer after the scores of the
 // current item -- instead of a cold load phase (5-6 k cycles at the ~11 B/clk a CU streams from HBM) and a launch gap (2 k) per item
@@ -871,7 +831,7 @@ __global__ __launch_bounds__(SF_THREADS, 2 * WG_PER_CU) void sgr_fused_persisten
         const bool meta_wave = has_next && wave >= 6;
         if (meta_wave && g.steps == 1)      // a single step is also the last one: the record must be there before its attention phase
             reinterpret_cast<int32_t *>(&m2[cur ^ 1])[tid - 384] = reinterpret_cast<const int32_t *>(g.meta + g.glist[nxt / g.nb])[tid - 384];
-        constexpr int LNR = ROWS > SF_SMALL ? ITR_SF_LNR : 4, LKB = ROWS > SF_SMALL ? ITR_SF_LKB : 4;
+        constexpr int LNR = ROWS > SF_SMALL ? SF_LNR : 4, LKB = ROWS > SF_SMALL ? SF_LKB : 4;
         float4 lw[LKB];          // first batch of the last step's weights: requested ahead of the barrier that precedes their projection
         constexpr bool early = ROWS > SF_SMALL;      // (two workgroups per CU: no registers to spare, and the other workgroup hides the trip)
         if (early && g.steps == 1) sf_last_weights0<LKB>(g.wqT_last, wave, lane, lw);
@@ -1011,7 +971,7 @@ static int sgr_cu_count(int64_t *cus) {
 
 // One class of groups.  ROWS = 32: two workgroups per CU; ROWS = 64: one.
 template <int ROWS, int WG_PER_CU>
-static int sgr_fused_launch_class(SgrFusedArgs g, int cls_index, int64_t n_groups, const SgrWs &w, bool persistent, const char *trace_path, hipStream_t st) {
+static int sgr_fused_launch_class(SgrFusedArgs g, int cls_index, int64_t n_groups, const SgrWs &w, bool persistent, hipStream_t st) {
     constexpr size_t lds = sf_lds_bytes(ROWS);
     int rc = allow_dynamic_lds(reinterpret_cast<const void *>(sgr_fused_kernel<ROWS, WG_PER_CU>), lds);
     if (rc == ITR_OK) rc = allow_dynamic_lds(reinterpret_cast<const void *>(sgr_fused_persistent_kernel<ROWS, WG_PER_CU>), lds);
@@ -1020,23 +980,6 @@ static int sgr_fused_launch_class(SgrFusedArgs g, int cls_index, int64_t n_group
     g.gcount = w.gcount + cls_index;
     const int64_t grid = n_groups * g.nb;                 // upper bound: the class's own count lives on the device
     ITR_REQUIRE(grid < (1ll << 31), "sgr_fused: grid too large");
-    if (trace_path) {
-        // Debug only (tools/sgr_trace.py): ITR_SGR_TRACE=<file> makes every launch synchronous and rewrites <file>.<class> with one record
-        // per workgroup (hardware id, group shape, s_memtime after every phase).
-        const size_t bytes = (size_t)grid * 20 * sizeof(unsigned long long);
-        ITR_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&g.trace), bytes));
-        ITR_CHECK_HIP(hipMemsetAsync(g.trace, 0, bytes, st));
-        hipLaunchKernelGGL((sgr_fused_kernel<ROWS, WG_PER_CU>), dim3((unsigned)grid), dim3(SF_THREADS), lds, st, g);
-        ITR_CHECK_LAUNCH("sgr_fused");
-        ITR_CHECK_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> host((size_t)grid * 20);
-        ITR_CHECK_HIP(hipMemcpy(host.data(), g.trace, bytes, hipMemcpyDeviceToHost));
-        ITR_CHECK_HIP(hipFree(g.trace));
-        char path[1024];
-        snprintf(path, sizeof(path), "%s.%d", trace_path, ROWS);
-        if (FILE *f = fopen(path, "wb")) { fwrite(host.data(), 1, bytes, f); fclose(f); }
-        return ITR_OK;
-    }
     if (persistent) {
         int64_t cus = 256;
         rc = sgr_cu_count(&cus);
@@ -1071,14 +1014,12 @@ int sgr_fused_scores(const float *xloc, const float *xglo, void *ws, int64_t n_g
     g.steps = sgr_step;
     g.wqT_last = w.wT;
     g.y0 = y0;
-    static const char *trace_env = ITR_EXP_ENV("ITR_SGR_TRACE");
-    const char *trace_path = (trace_env && *trace_env) ? trace_env : nullptr;
     const bool persistent = persistent_walk;      // (itr_sgraf_scores flag ITR_SGRAF_NON_PERSISTENT: one workgroup per (image, group))
     // the large class first (it is empty for every caption set of at most 31 words when the plan comes from itr_sgr_plan_node_groups:
     // its workgroups read a zero count and leave), then the small one
-    int rc = sgr_fused_launch_class<SF_ROWS, 1>(g, 1, n_groups, w, persistent, trace_path, st);
+    int rc = sgr_fused_launch_class<SF_ROWS, 1>(g, 1, n_groups, w, persistent, st);
     if (rc != ITR_OK) return rc;
-    return sgr_fused_launch_class<SF_SMALL, 2>(g, 0, n_groups, w, persistent, trace_path, st);
+    return sgr_fused_launch_class<SF_SMALL, 2>(g, 0, n_groups, w, persistent, st);
 }
 
 }  // namespace itr

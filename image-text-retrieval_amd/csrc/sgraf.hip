@@ -12,7 +12,6 @@
 // The global nodes img_glo / cap_glo (VisualSA :491-507, TextSA :543-559) are computed once per call.
 #include "scan_common.h"
 #include "itr_internal.h"
-#include <stdlib.h>
 
 namespace itr {
 
@@ -405,15 +404,6 @@ static inline int64_t sgraf_ib(int S, int64_t Ni, int image_block) {
 static inline bool sgraf_block_ok(int image_block) {
     return image_block == 0 || (image_block >= SC_IMGS && image_block <= 64 && image_block % SC_IMGS == 0);
 }
-// (ctx_glo - cap_glo)^2 rows of the global nodes: only the GEMM chain of sim_dim != 256 (experiment builds can select that chain at 256 too)
-static inline bool sgraf_needs_aglo(int S) {
-#ifdef ITR_EXPERIMENT
-    (void)S;
-    return true;
-#else
-    return S != 256;
-#endif
-}
 // the fused graph steps need neither the query nor the aggregate rows of the word nodes in memory (they live in the workgroup's LDS)
 static inline bool sgraf_fused_layout(int module, int S, int flags) { return module == 1 && S == 256 && !(flags & ITR_SGRAF_UNFUSED_STEPS); }
 
@@ -443,7 +433,7 @@ static SgrafWs sgraf_ws(void *base, int64_t Ni, int64_t Nc, int64_t n_rows, int6
     c.take((size_t)Nc * 8);                                                      // (unused slot)
     t.P = c.take<float>((size_t)IB * ncols * SC_R * 4), t.cn = c.take<float>((size_t)IB * ncols * 4), t.sscr = c.take<float>((size_t)IB * Nc * 4);
     if (S != 256) t.Aloc = c.take<float>((size_t)IB * ncols * D * 4);
-    if (sgraf_needs_aglo(S)) t.Aglo = c.take<float>((size_t)IB * Nc * D * 4);
+    if (S != 256) t.Aglo = c.take<float>((size_t)IB * Nc * D * 4);              // (ctx_glo - cap_glo)^2 rows of the global nodes' GEMM chain
     t.Pg = c.take<float>((size_t)IB * NcP * SC_R * 4), t.cng = c.take<float>((size_t)IB * NcP * 4);   // one-hot weights, unit norms
     t.gimg = c.take<float>((size_t)IB * SC_R * D * 4);                           // global "regions"
     t.Xloc = c.take<float>((size_t)IB * ncols * S * 4), t.Xglo = c.take<float>((size_t)IB * NcP * S * 4);
@@ -521,9 +511,9 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
     hipStream_t st = as_stream(stream);
     const int64_t ncols = n_tiles * SC_NT, IB = sgraf_ib(S, Ni, image_block);
     const int64_t NcP = (Nc + SC_NT - 1) / SC_NT * SC_NT;
-    // sim_dim 256: the global nodes come from the local-node kernel (ITR_SGRAF_GLO_GEMM=1: the (a - b)^2 kernel + GEMM + l2norm chain
-    // of rounds 1-2, for A/B timing); their rows then lie in whole 64-caption tiles: ldg = NcP rows per image
-    const bool glo_loc = (S == 256) && !ITR_EXP_ENV("ITR_SGRAF_GLO_GEMM");
+    // sim_dim 256: the global nodes come from the local-node kernel (other sizes: the (a - b)^2 kernel + GEMM + l2norm chain); their
+    // rows then lie in whole 64-caption tiles: ldg = NcP rows per image
+    const bool glo_loc = S == 256;
     const int64_t ldg = glo_loc ? NcP : Nc;
     int rc;
 #define SG_TRY(x) { rc = (x); if (rc != ITR_OK) return rc; }

@@ -23,8 +23,6 @@
 // stage 1 after stage 2 and then met a barrier: 127 -> 137 TFLOP/s (stage 1 + 2 flop, SGRAF 1k x 5k).
 #include "scan_common.h"
 #include "itr_internal.h"
-#include <stdlib.h>
-#include <vector>
 
 namespace itr {
 
@@ -40,7 +38,6 @@ struct LocArgs {
     float *X;              // [nb][ncols][256]  out: l2-normalised local nodes
     int64_t nb, n_tiles;
     int D;
-    unsigned long long *trace;   // debug (ITR_LOC_TRACE): [grid][5] = hardware id, s_memtime at entry / loop entry / loop exit / end
 };
 
 struct LocSmem {
@@ -60,7 +57,6 @@ __global__ __launch_bounds__(256, 2) void sgraf_loc_kernel(LocArgs g) {
     const int64_t xcd = bid & 7, idx = bid >> 3;
     const int64_t ct = (idx / g.nb) * 8 + xcd, ii = idx % g.nb;
     if (ct >= g.n_tiles) return;
-    const unsigned long long t_entry = g.trace ? __builtin_amdgcn_s_memtime() : 0ull;
     const int64_t ncols = g.n_tiles * SC_NT;
     const int64_t row0 = ii * ncols + ct * SC_NT;
     const int D = g.D;
@@ -108,16 +104,14 @@ __global__ __launch_bounds__(256, 2) void sgraf_loc_kernel(LocArgs g) {
     }
     f32x16 acc[2][2];
     const float *bias_lane = g.bias + wave * 64 + 4 * fg;      // the accumulators start at the bias (generated prologue)
-    const unsigned long long t_loop0 = g.trace ? __builtin_amdgcn_s_memtime() : 0ull;
     // The D loop: one generated asm statement (tools/gen_sgraf_loc.py has the schedule and the register map).
 #include "sgraf_loc_asm.inc"
-    const unsigned long long t_loop1 = g.trace ? __builtin_amdgcn_s_memtime() : 0ull;
 
     // ---- epilogue: l2norm over the 256 features of a row (utils.py:10-15, eps 1e-8), store.
     // The generated loop multiplies with swapped operands and starts from the bias, so acc[i][j] is the TRANSPOSED tile plus bias:
     // element r = feature wave*64 + 32 j + 8 (r >> 2) + 4 fg + (r & 3) of node row 32 i + fi -- a lane owns one row per i and runs
     // of four consecutive features.  What an instruction of this epilogue costs is its issue slot next to the co-resident
-    // workgroup's MFMA stream (~55 cycles each, tools/loc_trace.py: 48 000 cycles per workgroup for the first form, which stored
+    // workgroup's MFMA stream (~55 cycles each, measured with per-workgroup s_memtime stamps: 48 000 cycles per workgroup for the first form, which stored
     // 4-byte columns and exchanged all row sums through LDS; 25 000 for a version that transposed the tile through LDS), so the
     // count is what is minimised: packed squares and packed scaling (v_pk_fma_f32 / v_pk_mul_f32 on register pairs), one
     // v_permlane32_swap per row sum, 4 floats per lane through LDS for the cross-wave sums, sixteen 16-byte stores per lane.
@@ -161,15 +155,6 @@ __global__ __launch_bounds__(256, 2) void sgraf_loc_kernel(LocArgs g) {
                 *reinterpret_cast<float4 *>(out + 32 * j + 8 * b4) = float4{lo[0], lo[1], hi[0], hi[1]};
             }
     }
-    if (g.trace && tid == 0) {
-        // HW_REG_HW_ID (id 4): cu_id [11:8], sh_id [12], se_id [15:13]; HW_REG_XCC_ID (id 20): xcc_id [3:0]
-        const unsigned hw = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
-        const unsigned xcc = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the row stores are part of the workgroup's life
-        unsigned long long *t = g.trace + (size_t)blockIdx.x * 5;
-        t[0] = ((unsigned long long)xcc << 32) | hw;
-        t[1] = t_entry; t[2] = t_loop0; t[3] = t_loop1; t[4] = __builtin_amdgcn_s_memtime();
-    }
 }
 
 
@@ -181,34 +166,9 @@ int sgraf_loc_fused(const float *P, const float *cn, const float *img, const flo
         if (rc != ITR_OK) return rc;
     }
     if (nb == 0 || n_tiles == 0) return ITR_OK;
-    LocArgs g{P, cn, img, wtiled, W, bias, X, nb, n_tiles, D, nullptr};
+    LocArgs g{P, cn, img, wtiled, W, bias, X, nb, n_tiles, D};
     const int64_t grid = ceil_div(n_tiles, (int64_t)8) * 8 * nb;
-    // Debug only (tools/loc_trace.py): ITR_LOC_TRACE=<file> makes every launch synchronous and rewrites <file> with one record
-    // per workgroup (hardware id + four s_memtime stamps), from which the tool rebuilds each CU's timeline.
-    static const char *trace_path = ITR_EXP_ENV("ITR_LOC_TRACE");
-    // (experiment: ITR_LOC_ONE_PER_CU=1 asks for 82 KB of LDS, so only one workgroup fits a CU -- the loop's speed without a neighbour)
-    static const size_t lds_bytes = (ITR_EXP_ENV("ITR_LOC_ONE_PER_CU") && atoi(ITR_EXP_ENV("ITR_LOC_ONE_PER_CU"))) ? 82 * 1024 : sizeof(LocSmem);
-    if (lds_bytes != sizeof(LocSmem)) {
-        static bool big_done = false;
-        if (!big_done) {
-            ITR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sgraf_loc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            big_done = true;
-        }
-    }
-    if (trace_path && *trace_path) {
-        const size_t bytes = (size_t)grid * 5 * sizeof(unsigned long long);
-        ITR_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&g.trace), bytes));
-        ITR_CHECK_HIP(hipMemsetAsync(g.trace, 0, bytes, st));
-        hipLaunchKernelGGL(sgraf_loc_kernel, dim3((unsigned)grid), dim3(256), lds_bytes, st, g);
-        ITR_CHECK_LAUNCH("sgraf_loc");
-        ITR_CHECK_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> host((size_t)grid * 5);
-        ITR_CHECK_HIP(hipMemcpy(host.data(), g.trace, bytes, hipMemcpyDeviceToHost));
-        ITR_CHECK_HIP(hipFree(g.trace));
-        if (FILE *f = fopen(trace_path, "wb")) { fwrite(host.data(), 1, bytes, f); fclose(f); }
-        return ITR_OK;
-    }
-    hipLaunchKernelGGL(sgraf_loc_kernel, dim3((unsigned)grid), dim3(256), lds_bytes, st, g);
+    hipLaunchKernelGGL(sgraf_loc_kernel, dim3((unsigned)grid), dim3(256), sizeof(LocSmem), st, g);
     ITR_CHECK_LAUNCH("sgraf_loc");
     return ITR_OK;
 }

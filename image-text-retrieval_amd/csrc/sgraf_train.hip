@@ -747,9 +747,7 @@ static int sgt_lds(const void *kernel, size_t bytes, const char *what) {
 // 32, or all of S when S < 32).  16 KB: a graph's workgroup is a chain of staged chunks and barriers, so what hides it is the number of
 // graphs resident on the CU -- 32 KB (5 per CU, two chunks of S = 256) measured 20.4 ms on the SGR step, 16 KB (8 per CU, four chunks)
 // 20.05, 12 KB 20.2
-#ifndef SGT_GRAPH_LDS
-#define SGT_GRAPH_LDS (16 * 1024)
-#endif
+constexpr int64_t SGT_GRAPH_LDS = 16 * 1024;
 static int sgt_graph_chunk(int nmax, int S) {
     if (S <= 32) return S;
     int64_t room = (SGT_GRAPH_LDS / 4 - 2 * (int64_t)((nmax * nmax + 3) & ~3)) / (2 * (int64_t)nmax) - 4;

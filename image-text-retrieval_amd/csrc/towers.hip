@@ -8,7 +8,6 @@
 // into one MFMA GEMM [n_tok, E] x [E, 3D]; each time step is then one MFMA GEMM on the active
 // prefix (h[0:n_t] x W_hh^T) plus one fused gate kernel (sigmoid / tanh / state update / output
 // write, direction average and last-step gather folded in).
-#include <stdlib.h>
 #include "itr_internal.h"
 #include <mutex>
 #define ITR_SIDE_STREAM_IMPL
@@ -239,7 +238,7 @@ extern "C" int itr_gru_fwd(const int64_t *tokens, const int64_t *tok_off, const 
     const int Ep = pad32(E);
     // (split-K sums a dot product in slices: the result depends on the batch size through the slice count -- never with
     // ITR_GRU_BATCH_INVARIANT; the plain kernels all run the same fmaf chain per output element whatever M is)
-    const int splits_h = (B <= 1024 && !batch_invariant && !ITR_EXP_ENV("ITR_GRU_NO_SPLITK")) ? gemm_splitk_choice(B, 3 * D, D) : 1;   // env: A/B switch for tools/
+    const int splits_h = (B <= 1024 && !batch_invariant) ? gemm_splitk_choice(B, 3 * D, D) : 1;
     // The input projection of a token is a function of its ID alone: gi[token] = W_ih emb[id] + b_ih.  When the call has more tokens
     // than the vocabulary has words (an evaluation: 325 623 tokens over 11 353 words at 5k x 25k; Flickr30k 1k x 5k: 64 952 over 8 481)
     // the projection runs ONCE PER WORD -- a [V, Ep] x [Ep, 3D] GEMM into the head of the gi region -- and the gate kernel reads the
@@ -400,9 +399,9 @@ extern "C" int itr_gru_fwd(const int64_t *tokens, const int64_t *tok_off, const 
             ITR_CHECK_LAUNCH("gru_gate (both directions)");
         }
     }
-    // the reverse direction's recurrence on a second stream with its own buffers (ITR_GRU_NO_OVERLAP=1: one after the other, for A/B timing)
+    // the reverse direction's recurrence on a second stream with its own buffers
     SideStream side_obj;
-    SideStream *side = (bi && !paired && !ITR_EXP_ENV("ITR_GRU_NO_OVERLAP") && side_stream(side_obj)) ? &side_obj : nullptr;
+    SideStream *side = (bi && !paired && side_stream(side_obj)) ? &side_obj : nullptr;
     if (side) {
         ITR_CHECK_HIP(hipEventRecord(side->fork, st));
         ITR_CHECK_HIP(hipStreamWaitEvent(side->st, side->fork, 0));

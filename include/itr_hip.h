@@ -316,8 +316,6 @@ int itr_sgraf_scores(const float *img, const float *words, const int64_t *cap_of
                      const int32_t *node_group_order_dev, int64_t n_node_groups, int image_block, int flags, float *S_out,
                      int64_t ldS, void *workspace, size_t workspace_bytes, itr_stream_t stream);
 
-/* diagnostics (tools/): occupancy of the SCAN kernel as reported by the HIP runtime */
-int itr_debug_scan_occupancy(int *blocks_per_cu, int *lds_bytes);
 /* diagnostics (bench.py's sustained-clock probe): one INSTRUMENTED launch of the SCAN kernel with the arguments of
  * itr_scan_xattn_scores.  `scratch` [Ni, ld_scratch >= Nc + 64] is not a score matrix afterwards: its first 64 bytes hold eight
  * uint64 counters summed over all workgroups -- [0..6] shader-clock cycles (s_memtime) per phase, [7] 100 MHz ticks

@@ -13,9 +13,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import audit_asm_loads as A  # noqa: E402
 
 CSRC = os.path.join(ROOT, "image-text-retrieval_amd", "csrc")
-# (source, kernels that must be present and clean).  Not listed: scan_xattn_kernel<5> / <9> (ablation builds of tools/) and <3>
-# (opt-in fp16x3 study variant: it drains inside its LAST chunk under `if (kc >= klast)`, which is correlated with the loop
-# exit -- a union-at-joins dataflow cannot prove that, it reports the park code after the loop).
+# (source, kernels that must be present and clean).  Not listed: scan_xattn_kernel<3> (opt-in fp16x3 study variant: it drains
+# inside its LAST chunk under `if (kc >= klast)`, which is correlated with the loop exit -- a union-at-joins dataflow cannot
+# prove that, it reports the park code after the loop).
 CASES = [("scan_xattn.hip", ["scan_xattn_kernelILi0E", "scan_xattn_kernelILi1E"]),
          ("gemm_f32.hip", ["gemm_nt_fast_kernel"]),
          ("gemm_stream.hip", ["gemm_nt_stream_kernelILi0E", "gemm_nt_stream_kernelILi1E", "gemm_nt_stream_kernelILi4E"]),

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A side-by-side build of an EARLIER commit under tools/ab/<name> (git-ignored; it travels to the GPU box with gpurun), for same-box
-# interleaved A/B runs against this tree (tools/ab_run.sh, tools/ab_sgr.sh):   tools/ab_checkout.sh 0807f13 r3
+# interleaved A/B runs against this tree (tools/ab_two.sh, tools/ab_multi.sh):   tools/ab_checkout.sh 0807f13 r3
 set -e
 COMMIT=$1; NAME=$2
 DST=tools/ab/$NAME

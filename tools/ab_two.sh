@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX: same-box, interleaved A/B of one bench workload: a side-by-side build under tools/ab/<name> (tools/ab_checkout.sh
-# <commit> <name> or tools/ab_build.sh <name> <flags>) against this tree.   tools/ab_two.sh <name> <workload> <out dir> [rounds] [steps]
+# <commit> <name>) against this tree.   tools/ab_two.sh <name> <workload> <out dir> [rounds] [steps]
 NAME=${1:-base}; WL=${2:-sgraf_sgr_f30k1k}; OUT=${3:-gpurun_out/ab}; N=${4:-2}; STEPS=${5:-5}
 mkdir -p $OUT
 ARGS="--workload $WL --steps $STEPS --warmup 2 --no-cpu-baseline --no-variants --no-other-configs"

@@ -3,7 +3,7 @@
 B sequences x L positions x 12 heads x 64, q / k / v column slices of one fused QKV buffer.  Prints time, effective bandwidth
 (q + k + v read, context written) and a checksum; the result is checked against a float64 torch reference on the first sequences.
 
-    python3 tools/mha_bench.py [B] [L]            (run on the GPU box; ITR_MHA_LDS=1: the LDS-staged kernel instead of the register-only one)"""
+    python3 tools/mha_bench.py [B] [L]            (run on the GPU box)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "image-text-retrieval_amd"))
