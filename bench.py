@@ -14,10 +14,15 @@ resident in HBM:   image projection + l2norm -> embedding + bi-GRU -> [all-gathe
 The 5k x 25k score matrix is row-sharded over ranks (strong scaling: total work is fixed).
 Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else.  Everything else the
+line can carry runs only with --full, after the timed steps: the CPU baseline and its Recall parity check, the fp16x3 study
+variant, the sustained-clock probe, the short runs of the other BASELINE.json configs, the training-step timings and the
+materialised re-run of --stream-scores.  Each --no-* switch drops its part of a --full run.
+
 Exit codes: 0 clean run; 2 refused launch (--gpus / WORLD_SIZE / device count mismatch); 3 the ranks missed the initialisation
-deadline and 4 Recall parity against the CPU sample failed (the line is still printed); 5 --launch-check: a fabric collective
-failed; 6 the primary line was printed but a SECONDARY config hung (N > 1: asymmetric failure inside a collective) -- rank 0's
-watchdog ended the process, the peers end by ITR_DIST_TIMEOUT_S.
+deadline and 4 Recall parity against the CPU sample failed (--full; the line is still printed); 5 --launch-check: a fabric
+collective failed; 6 the primary line was printed but a SECONDARY config hung (--full, N > 1: asymmetric failure inside a
+collective) -- rank 0's watchdog ended the process, the peers end by ITR_DIST_TIMEOUT_S.
 """
 import argparse
 import json
@@ -523,7 +528,8 @@ def main_pooled(args, wl, world, rank, dev, use_dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     streamed = S is None
-    if streamed and world == 1:
+    streamed_equal = None
+    if streamed and world == 1 and args.full:
         # outside the timed region: the same evaluation with the matrix kept -- the parity legs below read it, and its ranks must be
         # the streamed ones, entry for entry
         S, ranks_kept = step(None, keep=True)
@@ -582,16 +588,17 @@ def main_pooled(args, wl, world, rank, dev, use_dist):
                                 "recurrence product); algorithmic_equiv_frac = SURVEY 8d's flop over the same time"}}
     if streamed and world == 1:
         out["score_matrix"] = {"materialised": False, "row_block_bytes": 64 << 20,
-                               "ranks_equal_materialised_run": bool(streamed_equal),
-                               "note": "timed steps stream the similarity matrix through the ranker in row blocks (evalpipe.score_rank_streamed); "
-                                       "a run that keeps the matrix (after the timed region) gave the same rank vectors"}
-        if not streamed_equal:
-            print("bench.py: the streamed ranks differ from the ranks of the materialised matrix", file=sys.stderr)
+                               "note": "timed steps stream the similarity matrix through the ranker in row blocks (evalpipe.score_rank_streamed)"}
+        if streamed_equal is not None:
+            out["score_matrix"]["ranks_equal_materialised_run"] = bool(streamed_equal)
+            out["score_matrix"]["note"] += "; a run that keeps the matrix (after the timed region) gave the same rank vectors"
+            if not streamed_equal:
+                print("bench.py: the streamed ranks differ from the ranks of the materialised matrix", file=sys.stderr)
     if comm.virtual:
         out["virtual_split"] = "%d:%d" % (comm.cap_world, comm.cap_rank)
         out["config"]["parallelism"] = "1 process, caption axis split over %d virtual owners (this one: %d): TEST HOOK, time is not a result" % (
             comm.cap_world, comm.cap_rank)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # CPU oracle (kind "port") on the first ns images and their 5*ns captions: encode + score + rank, and max |diff|
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import itr_oracle as O
@@ -943,8 +950,7 @@ def other_config_in_child(name, k, w, timeout_s):
     secondary config cannot take the already-measured primary line with it, and the child starts from an empty
     memory pool like any user's process would.  -> (result dict | None, error string | None)."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(k), "--warmup", str(w), "--no-cpu-baseline",
-           "--no-variants", "--no-other-configs"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(k), "--warmup", str(w)]      # a plain run
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("ITR_BENCH_PROGRESS_DIR",)}
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout_s)
@@ -985,20 +991,25 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the separately reported fp16x3 variant of the SCAN workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the CPU baseline with its Recall parity "
+                         "check (exit 4), the fp16x3 variant, the sustained-clock probe, the other BASELINE.json configs, the training-step "
+                         "timings and the materialised re-run of --stream-scores (the --no-* switches drop parts of it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its Recall parity check")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the separately reported fp16x3 variant of the SCAN workloads")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short runs of the other BASELINE.json configs that the default workload's line carries in `other_configs`")
+                    help="--full: skip the short runs of the other BASELINE.json configs that the default workload's line carries in "
+                         "`other_configs` (and the training-step timings)")
     ap.add_argument("--stream-scores", action="store_true",
                     help="pooled workloads, one process: the timed steps stream the similarity matrix through the ranker in row blocks instead "
                          "of storing it (evalpipe.score_rank_streamed); measured slower, off by default")
     ap.add_argument("--no-train-configs", action="store_true",
-                    help="skip the training-step timings (model.train_emb of every family, tools/train_bench.py in a child process) that the "
-                         "default workload's line carries in `train_configs`")
-    ap.add_argument("--cpu-sample-images", type=int, default=160)
-    ap.add_argument("--cpu-repeats", type=int, default=3, help="passes of the CPU leg (the minimum is reported, with the spread)")
+                    help="--full: skip the training-step timings (model.train_emb of every family, tools/train_bench.py in a child process) "
+                         "that the default workload's line carries in `train_configs`")
+    ap.add_argument("--cpu-sample-images", type=int, default=160, help="--full: images of the CPU leg's sample block")
+    ap.add_argument("--cpu-repeats", type=int, default=3, help="--full: passes of the CPU leg (the minimum is reported, with the spread)")
     ap.add_argument("--cpu-threads", default=None, metavar="N[,N...]",
-                    help="thread counts of the CPU leg (default: torch's own count and 64 / 32 / 16 where the host has more)")
+                    help="--full: thread counts of the CPU leg (default: torch's own count and 64 / 32 / 16 where the host has more)")
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, build the process group, all-gather the rank table, run the exchange's two collectives on their "
                          "real payload sizes (fabric check), print the line with value = null and stop (no kernel of the path runs)")
@@ -1137,10 +1148,10 @@ def main():
             if rp is not None and not rp["ok"]:
                 print("bench.py: Recall parity FAILED: |dR@K| = %.3f > %.1f on the CPU sample block" % (rp["max_abs_recall_diff"], RECALL_TOL), file=sys.stderr)
                 rc = 4
-        if args.workload == DEFAULT_WORKLOAD and not args.no_other_configs and not args.virtual_split:
+        if args.full and args.workload == DEFAULT_WORKLOAD and not args.no_other_configs and not args.virtual_split:
             other_configs(args, world, rank, dev, use_dist, backend, line)
-        if (args.workload == DEFAULT_WORKLOAD and not args.no_train_configs and not args.no_other_configs and not args.virtual_split and world == 1
-                and not use_dist and dev.type == "cuda" and os.environ.get("ITR_BENCH_OTHER") != "small"):
+        if (args.full and args.workload == DEFAULT_WORKLOAD and not args.no_train_configs and not args.no_other_configs and not args.virtual_split
+                and world == 1 and not use_dist and dev.type == "cuda" and os.environ.get("ITR_BENCH_OTHER") != "small"):
             progress("train_configs")
             line.out["train_configs"] = train_configs_in_child(240)
     finally:
@@ -1194,10 +1205,9 @@ def other_configs(args, world, rank, dev, use_dist, backend, line):
                 o, err = other_config_in_child(name, k, w, 240)
                 ok = int(o is not None)
             else:
-                a2 = argparse.Namespace(**dict(vars(args), workload=name, steps=k, warmup=w, no_cpu_baseline=True, no_variants=True,
-                                               dump_outputs=None))
+                a2 = argparse.Namespace(**dict(vars(args), workload=name, steps=k, warmup=w, full=False, dump_outputs=None))
                 try:
-                    o = run_workload(a2, world, rank, dev, use_dist, backend, primary=False)
+                    o = run_workload(a2, world, rank, dev, use_dist, backend)
                 except Exception as e:      # noqa: BLE001
                     ok, err = 0, "%s: %s" % (type(e).__name__, e)
             flag = torch.tensor([ok, int(time.perf_counter() - t_other < 300.0)], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
@@ -1217,20 +1227,20 @@ def other_configs(args, world, rank, dev, use_dist, backend, line):
             wd.cancel()
 
 
-def run_workload(args, world, rank, dev, use_dist, backend, primary=True):
+def run_workload(args, world, rank, dev, use_dist, backend):
     """One workload, timed as the contract says (W untimed steps, barrier + synchronize, K steps, barrier + synchronize, MAX over
-    ranks).  Returns the result dict on rank 0 and None elsewhere.  `primary` = False: no CPU leg, no study variant, no clock probe."""
+    ranks).  Returns the result dict on rank 0 and None elsewhere.  Without args.full: no CPU leg, no study variant, no clock probe."""
     import gc
     try:
         if "pooled" in WORKLOADS[args.workload]:
             return main_pooled(args, WORKLOADS[args.workload], world, rank, dev, use_dist)
-        return main_words(args, world, rank, dev, use_dist, backend, primary)
+        return main_words(args, world, rank, dev, use_dist, backend)
     finally:
         gc.collect()
         torch.cuda.empty_cache()      # the next workload starts from an empty pool, like a fresh process would
 
 
-def main_words(args, world, rank, dev, use_dist, backend, primary=True):
+def main_words(args, world, rank, dev, use_dist, backend):
     """The word-level scorers: SCAN (t2i / i2t) and SGRAF (SAF / SGR) on bi-GRU word embeddings."""
     from itr_amd import evalpipe, ops
     wl = WORKLOADS[args.workload]
@@ -1257,7 +1267,7 @@ def main_words(args, world, rank, dev, use_dist, backend, primary=True):
     cap_ranges = evalpipe.caption_ranges(n_cap, comm.cap_world, lengths)      # near-equal TOKEN sums per owner
     c0, c1 = cap_ranges[comm.cap_rank]
     feats_local = feats[i0:i1].contiguous()
-    feats_head = feats[:args.cpu_sample_images].cpu() if rank == 0 else None
+    feats_head = feats[:args.cpu_sample_images].cpu() if args.full and rank == 0 else None
     del feats
     toks, tok_off, lens_sorted, order = shard_captions(lengths, tokens, c0, c1, dev)
     model = evalpipe.GruModelEval({k: v.to(dev) for k, v in wi.items()}, {k: v.to(dev) for k, v in wt.items()}, cfg, comm)
@@ -1309,7 +1319,7 @@ def main_words(args, world, rank, dev, use_dist, backend, primary=True):
     per_rank = gather_floats([min(step_ms), max(step_ms), float(np.mean(step_ms)), float(np.mean(scan_ms)), wait_ms], dev, backend, use_dist)
 
     if rank == 0:
-        if primary and getattr(args, "dump_outputs", None):
+        if args.dump_outputs:
             dump_outputs(args.dump_outputs, S, ranks, i0)
         ms_per_step = 1e3 * dt / args.steps
         pairs = float(n_img) * n_cap
@@ -1394,7 +1404,7 @@ def main_words(args, world, rank, dev, use_dist, backend, primary=True):
             out["virtual_split"] = "%d:%d" % (comm.cap_world, comm.cap_rank)
             out["config"]["parallelism"] = "1 process, caption axis split over %d virtual owners (this one: %d): TEST HOOK, time is not a result" % (
                 comm.cap_world, comm.cap_rank)
-        if primary and world == 1 and not is_sgraf and "scan_precision" not in wl and not comm.virtual:
+        if args.full and world == 1 and not is_sgraf and "scan_precision" not in wl and not comm.virtual:
             # the peak is quoted at 2 400 MHz; the chip sustains less under this kernel (power management): measured in-kernel
             try:
                 mhz = scan_sustained_clock(model, feats_local, toks, tok_off, lens_sorted, order, cfg, dev)
@@ -1406,7 +1416,7 @@ def main_words(args, world, rank, dev, use_dist, backend, primary=True):
                 out["roofline"]["frac_of_sustained_clock_peak"] = out["roofline"]["frac"] * 2400.0 / mhz
                 out["roofline"]["clock_note"] = ("s_memtime / s_memrealtime summed over every workgroup of one extra instrumented launch; "
                                                  "frac uses the 2 400 MHz peak, frac_of_sustained_clock_peak the clock the chip actually ran at")
-        if primary and world == 1 and not is_sgraf and "scan_precision" not in wl and not args.no_variants and not comm.virtual:
+        if args.full and world == 1 and not is_sgraf and "scan_precision" not in wl and not args.no_variants and not comm.virtual:
             # Reported NEXT TO the exact-fp32 metric, never instead of it (STUDY_SPLIT_PRECISION.md): the same step with the region x word dot
             # products from split fp16 operands (hi.hi + hi.lo' + lo'.hi, fp32 accumulation) -- outside the timed region above
             vmodel = evalpipe.GruModelEval(model.wi, model.wt, dict(cfg, scan_precision="fp16x3"), comm)
@@ -1430,7 +1440,7 @@ def main_words(args, world, rank, dev, use_dist, backend, primary=True):
                 "note": "opt-in study variant, reported separately: fp32 inputs split into scaled fp16 hi + lo planes, 3 fp16 MFMA products, "
                         "fp32 accumulate; against a float64 oracle it is not further from the truth than the fp32 kernel (STUDY_SPLIT_PRECISION.md)"}
             del Sv
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base, S_cpu = cpu_baseline(wl, wi, wt, feats_head, lengths, tokens, args.cpu_sample_images, args.cpu_repeats)
             ns, ncs = args.cpu_sample_images, 5 * args.cpu_sample_images
             base["max_abs_diff_vs_gpu"] = float((S[:ns, :ncs].cpu() - S_cpu).abs().max())
@@ -1444,7 +1454,7 @@ def main_words(args, world, rank, dev, use_dist, backend, primary=True):
             if base.get("fold_value"):
                 out["speedup_vs_cpu_fold"] = out["value"] / base["fold_value"]
                 out["speedup_vs_cpu_fold_basis"] = base["fold_source"]
-        elif world > 1 and not args.no_cpu_baseline:
+        elif args.full and world > 1 and not args.no_cpu_baseline:
             rec = cpu_baseline_replayed(args.workload)
             if rec is not None:
                 out["cpu_baseline"] = rec

@@ -296,7 +296,8 @@ def test_bench_gpus_2_as_one_command_on_one_gpu():
 def test_other_configs_ride_along_with_the_default_line():
     """the default workload's line carries a timed figure for every other BASELINE.json config.  Run here on the
     small default (ITR_BENCH_OTHER=small keeps the 1k x 5k forms only, so the test stays short)."""
-    out = _bench_line(["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-variants"], env=dict(ITR_BENCH_OTHER="small"), timeout=1500)
+    out = _bench_line(["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-variants"], env=dict(ITR_BENCH_OTHER="small"),
+                      timeout=1500)
     oc = out["other_configs"]
     assert set(oc) >= {"vsepp_f30k1k", "scan_t2i_f30k1k", "sgraf_saf_f30k1k", "sgraf_sgr_f30k1k"}
     for name, o in oc.items():
@@ -310,8 +311,9 @@ def test_other_configs_ride_along_with_the_default_line():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-                        "--no-variants"], env=dict(env, ITR_DIST_BACKEND="gloo", ITR_BENCH_OTHER="small"), capture_output=True, text=True, timeout=1500)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "1", "--warmup", "0",
+                        "--no-cpu-baseline", "--no-variants"], env=dict(env, ITR_DIST_BACKEND="gloo", ITR_BENCH_OTHER="small"), capture_output=True,
+                       text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     two = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][0])
     assert two["n_gpus"] == 2 and two["rank_checksum"] == out["rank_checksum"]
@@ -321,13 +323,24 @@ def test_other_configs_ride_along_with_the_default_line():
 
 
 @pytest.mark.gpu
+def test_plain_run_measures_only_the_headline():
+    """Without --full the default workload's run stops after its timed steps: the line carries the headline figure and what the
+    steps themselves gave, and none of the CPU leg, the fp16x3 variant, the clock probe, the other configs or the training timings."""
+    out = _bench_line(["--steps", "1", "--warmup", "0"])
+    assert out["config"]["workload"] == "scan_t2i_coco5k" and out["steps"] == 1 and out["ms_per_step"] > 0 and len(out["rank_checksum"]) == 4
+    for key in ("cpu_baseline", "speedup_vs_cpu_baseline", "variant_fp16x3", "other_configs", "train_configs"):
+        assert key not in out, key
+    assert "sustained_clock_mhz" not in out["roofline"] and out["roofline"]["frac"] > 0
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("workload", ["scan_t2i_f30k1k", "vsepp_f30k1k", "sgraf_saf_f30k1k"])
 def test_bench_line_carries_recall_parity_and_a_repeatable_cpu_baseline(workload):
     """the metric is "pairs/sec + Recall@1 parity" -- the line's cpu_baseline carries Recall@1/5/10 of the
     reference's argsort ranker on the CPU path's scores next to the HIP ranker's on the HIP path's scores for the same sample
     block (|dR@K| <= 0.1 or the run exits 4), the HIP ranker alone reproduces the argsort rank vectors on the CPU's matrix, and the
     CPU leg is timed more than once with the host it ran on recorded."""
-    out = _bench_line(["--workload", workload, "--steps", "1", "--warmup", "0", "--no-variants", "--no-other-configs",
+    out = _bench_line(["--full", "--workload", workload, "--steps", "1", "--warmup", "0", "--no-variants", "--no-other-configs",
                        "--cpu-sample-images", "40", "--cpu-repeats", "2"])
     cb = out["cpu_baseline"]
     rp = cb["recall_parity"]
@@ -354,7 +367,7 @@ def test_launch_check_runs_the_exchange_collectives_over_rccl():
 def test_fp16x3_variant_rides_along_with_the_single_gpu_line():
     """The separately reported split-fp16 variant of the SCAN workloads: fp32-level scores, same Recall@K, reported next to
     (never instead of) the fp32 line."""
-    single = _bench_line(["--workload", "scan_t2i_f30k1k", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
+    single = _bench_line(["--full", "--workload", "scan_t2i_f30k1k", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
     v = single["variant_fp16x3"]
     assert v["max_abs_diff_vs_fp32_scores"] <= 1e-5 and v["recall"] == single["recall"]
 

@@ -5,12 +5,12 @@ OUT=gpurun_out/bench_$TAG
 mkdir -p $OUT
 cd /tmp 2>/dev/null; cd - >/dev/null
 export TMPDIR=/tmp
-python3 bench.py > $OUT/scan_t2i_coco5k.json 2> $OUT/scan_t2i_coco5k.err
+python3 bench.py --full > $OUT/scan_t2i_coco5k.json 2> $OUT/scan_t2i_coco5k.err
 for w in scan_i2t_coco5k vsepp_f30k1k vsrn_coco5k saem_coco5k camera_coco5k sgraf_saf_f30k1k sgraf_sgr_f30k1k sgraf_saf_coco5k sgraf_sgr_coco5k scan_t2i_f30k1k; do
   # a 10-50 ms step needs more than three of them: the first steps after the warm-up still run at the idle clock (VSE++ f30k: 11.1 ms
   # with --steps 3 --warmup 1, 10.0 ms with 20 / 5 on the same box)
   case $w in vsepp_f30k1k|scan_t2i_f30k1k) SW="--steps 20 --warmup 5";; *) SW="--steps 3 --warmup 1";; esac
-  timeout 900 python3 bench.py --workload $w $SW --no-variants > $OUT/$w.json 2> $OUT/$w.err
+  timeout 900 python3 bench.py --workload $w $SW --full --no-variants > $OUT/$w.json 2> $OUT/$w.err
 done
 python3 tools/make_synth_precomp.py /tmp/itr_synth --n-img 5000 > /dev/null && timeout 600 python3 bench.py --from-files /tmp/itr_synth --steps 3 --warmup 1 > $OUT/scan_t2i_coco5k_from_files.json 2> $OUT/from_files.err
 for w in camera_coco5k saem_coco5k vsepp_f30k1k sgraf_saf_f30k1k sgraf_sgr_f30k1k vsrn_coco5k; do
