@@ -391,20 +391,26 @@ def sgraf_similarity(w, img_emb, cap_emb, cap_lens, module_name='SAF', sgr_step=
 # --------------------------------------------------------------------------------------
 
 
-def _bn_train(x, w, p, channel_dim, eps=1e-5):
+def _bn_train(x, w, p, channel_dim, eps=1e-5, bn_stats=None):
+    """bn_stats: None, or a list that receives (p, batch mean, biased batch variance, values per channel) of this call, detached --
+    what torch's BatchNorm folds into its running statistics."""
     dims = [d for d in range(x.dim()) if d != channel_dim]
     mean = x.mean(dims, keepdim=True)
     var = x.var(dims, unbiased=False, keepdim=True)
+    if bn_stats is not None:
+        bn_stats.append((p, mean.detach().reshape(-1), var.detach().reshape(-1), x.numel() // x.shape[channel_dim]))
     shape = [1] * x.dim()
     shape[channel_dim] = -1
     return (x - mean) / torch.sqrt(var + eps) * w[p + '.weight'].view(shape) + w[p + '.bias'].view(shape)
 
 
-def sgraf_similarity_train(w, img_emb, cap_emb, cap_lens, module_name='SAF', sgr_step=3):
-    """EncoderSimilarity.forward (Fusionmodule.py:406-451) in training mode -> (Ni, Nc).  Same loop over the captions as the reference."""
+def sgraf_similarity_train(w, img_emb, cap_emb, cap_lens, module_name='SAF', sgr_step=3, bn_stats=None):
+    """EncoderSimilarity.forward (Fusionmodule.py:406-451) in training mode -> (Ni, Nc).  Same loop over the captions as the reference.
+    bn_stats: None, or a list that receives every BatchNorm call's batch statistics in call order (_bn_train)."""
     n_image = img_emb.shape[0]
-    l_emb = torch.tanh(_bn_train(_linear(img_emb, w, 'v_global_w.embedding_local.0'), w, 'v_global_w.embedding_local.1', 1))
-    g_emb = torch.tanh(_bn_train(_linear(img_emb.mean(1), w, 'v_global_w.embedding_global.0'), w, 'v_global_w.embedding_global.1', 1))
+    l_emb = torch.tanh(_bn_train(_linear(img_emb, w, 'v_global_w.embedding_local.0'), w, 'v_global_w.embedding_local.1', 1, bn_stats=bn_stats))
+    g_emb = torch.tanh(_bn_train(_linear(img_emb.mean(1), w, 'v_global_w.embedding_global.0'), w, 'v_global_w.embedding_global.1', 1,
+                                 bn_stats=bn_stats))
     weights = torch.softmax(_linear(l_emb * g_emb.unsqueeze(1), w, 'v_global_w.embedding_common.0').squeeze(2), dim=1)
     img_glo = l2norm((weights.unsqueeze(2) * img_emb).sum(1), dim=-1)
     cols = []
@@ -427,7 +433,7 @@ def sgraf_similarity_train(w, img_emb, cap_emb, cap_lens, module_name='SAF', sgr
             sim_vec = sim_emb[:, 0]
         elif module_name == 'SAF':
             a = _linear(sim_emb, w, 'SAF_module.attn_sim_w').transpose(1, 2)          # (Ni, 1, nw + 1)
-            a = l1norm(torch.sigmoid(_bn_train(a, w, 'SAF_module.bn', 1)), dim=-1)
+            a = l1norm(torch.sigmoid(_bn_train(a, w, 'SAF_module.bn', 1, bn_stats=bn_stats)), dim=-1)
             sim_vec = l2norm(torch.bmm(a, sim_emb).squeeze(1), dim=-1)
         else:
             raise ValueError('Invalid input of config.module_name in configs.py')
@@ -435,11 +441,13 @@ def sgraf_similarity_train(w, img_emb, cap_emb, cap_lens, module_name='SAF', sgr
     return torch.stack(cols, 1)
 
 
-def sgraf_model_train_grads(wi, wt, ws, images, ids, lengths, cfg):
+def sgraf_model_train_grads(wi, wt, ws, images, ids, lengths, cfg, out=None):
     """One SGRAF.train_emb step up to the clipped gradients (Models.py:524-546): towers -> training-mode similarity -> hinge ->
     backward -> clip_grad_norm_.  wi: {'fc.weight', 'fc.bias'}; wt: EncoderText state_dict; ws: EncoderSimilarity state_dict
     (parameters and BatchNorm buffers).  Returns (loss, {name: clipped gradient}) with names 'img.<k>' / 'txt.<k>' / 'sim.<k>'.
-    Parameter order as the reference builds it: txt_enc, img_enc, sim_enc (Models.py:498-500)."""
+    Parameter order as the reference builds it: txt_enc, img_enc, sim_enc (Models.py:498-500).
+    out: None, or a dict that receives 'scores' (the similarity matrix), 'grad_norm' (the total norm before clipping) and 'bn_stats'
+    (every BatchNorm call's batch statistics, sgraf_similarity_train)."""
     is_param = lambda k: not (k.endswith('running_mean') or k.endswith('running_var') or k.endswith('num_batches_tracked'))
     names = [('txt.' + k, wt, k) for k in wt] + [('img.' + k, wi, k) for k in ('fc.weight', 'fc.bias')] + \
             [('sim.' + k, ws, k) for k in ws if is_param(k)]
@@ -450,12 +458,16 @@ def sgraf_model_train_grads(wi, wt, ws, images, ids, lengths, cfg):
         ws_l = {k: (leaves['sim.' + k] if is_param(k) else ws[k]) for k in ws}
         img = encoder_image_precomp(images, wi_l['fc.weight'], wi_l['fc.bias'], cfg.get('no_imgnorm', False))
         cap, cap_len = encoder_text(ids, lengths, wt_l, bool(cfg.get('bi_gru', False)), cfg.get('no_txtnorm', False), False, None)
-        sims = sgraf_similarity_train(ws_l, img, cap, cap_len, cfg.get('module_name', 'SAF'), cfg.get('sgr_step', 3))
+        bn_stats = [] if out is not None else None
+        sims = sgraf_similarity_train(ws_l, img, cap, cap_len, cfg.get('module_name', 'SAF'), cfg.get('sgr_step', 3), bn_stats=bn_stats)
         loss = hinge_loss(sims, cfg.get('margin', 0.2), cfg.get('max_violation', False))
         loss.backward()
     grads = [leaves[n].grad if leaves[n].grad is not None else torch.zeros_like(leaves[n]) for n, _, _ in names]
+    total = None
     if cfg.get('grad_clip', 2.0) > 0:
-        grads, _ = clip_grad_norm(grads, cfg.get('grad_clip', 2.0))
+        grads, total = clip_grad_norm(grads, cfg.get('grad_clip', 2.0))
+    if out is not None:
+        out.update(scores=sims.detach(), grad_norm=total, bn_stats=bn_stats)
     return loss.detach(), {n: g for (n, _, _), g in zip(names, grads)}
 
 
@@ -775,10 +787,12 @@ def adam_update(p, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
     return p - (lr / bc1) * (m / denom), m, v
 
 
-def gru_model_loss(kind, wi, wt, images, ids, lengths, cfg):
+def gru_model_loss(kind, wi, wt, images, ids, lengths, cfg, out=None):
     """Training-mode forward of the GRU model family on one batch -> scalar loss.
     kind 'SCAN': region embeddings x word embeddings -> xattn_score -> hinge (Models.py:182-205);
-    kind 'VSE++': mean-pooled regions (SURVEY Q3 build decision) x last GRU state -> cosine -> hinge."""
+    kind 'VSE++': mean-pooled regions (SURVEY Q3 build decision) x last GRU state -> cosine -> hinge; VSE++ builds its text tower
+    with no_txtnorm=False whatever the config says (Models.py:79), so its caption vectors are always l2-normalised.
+    out: None, or a dict that receives 'scores' (the score matrix the hinge reads)."""
     bi = bool(cfg.get('bi_gru', False))
     if kind == 'SCAN':
         img = encoder_image_precomp(images, wi['fc.weight'], wi['fc.bias'], cfg.get('no_imgnorm', False))
@@ -787,28 +801,33 @@ def gru_model_loss(kind, wi, wt, images, ids, lengths, cfg):
                              cfg.get('agg_func', 'LogSumExp'), cfg.get('lambda_lse', 6.0), cfg.get('lambda_softmax', 9.0))
     elif kind == 'VSE++':
         img = encoder_image_precomp(images.mean(1), wi['fc.weight'], wi['fc.bias'], cfg.get('no_imgnorm', False))
-        cap, _ = encoder_text(ids, lengths, wt, bi, cfg.get('no_txtnorm', False), False, 'VSE++')
+        cap, _ = encoder_text(ids, lengths, wt, bi, False, False, 'VSE++')
         scores = cosine_sim(img, cap)
     else:
         raise ValueError(kind)
+    if out is not None:
+        out['scores'] = scores.detach()
     return hinge_loss(scores, cfg.get('margin', 0.2), cfg.get('max_violation', False))
 
 
-def gru_model_train_step(kind, wi, wt, images, ids, lengths, cfg, state=None):
+def gru_model_train_step(kind, wi, wt, images, ids, lengths, cfg, state=None, out=None):
     """One train_emb step.  wi: {'fc.weight', 'fc.bias'}; wt: EncoderText state_dict.  state: None or
     {'t': int, 'm': {name: tensor}, 'v': {...}} with names 'txt.<k>' / 'img.<k>'.
     Returns (loss, clipped grads dict, new wi, new wt, new state).  Parameter order as the reference builds
-    it: txt_enc.parameters() then img_enc.fc.parameters() (Models.py:95-97, :175-177)."""
+    it: txt_enc.parameters() then img_enc.fc.parameters() (Models.py:95-97, :175-177).
+    out: None, or a dict that receives 'scores' (gru_model_loss) and 'grad_norm' (the total norm before clipping)."""
     names = [('txt.' + k, wt, k) for k in wt] + [('img.' + k, wi, k) for k in ('fc.weight', 'fc.bias')]
     with torch.enable_grad():
         leaves = {n: d[k].detach().clone().requires_grad_(True) for n, d, k in names}
         wi_l = {k: leaves['img.' + k] for k in ('fc.weight', 'fc.bias')}
         wt_l = {k: leaves['txt.' + k] for k in wt}
-        loss = gru_model_loss(kind, wi_l, wt_l, images, ids, lengths, cfg)
+        loss = gru_model_loss(kind, wi_l, wt_l, images, ids, lengths, cfg, out=out)
         loss.backward()
     grads = [leaves[n].grad if leaves[n].grad is not None else torch.zeros_like(leaves[n]) for n, _, _ in names]
     if cfg.get('grad_clip', 2.0) > 0:
-        grads, _ = clip_grad_norm(grads, cfg.get('grad_clip', 2.0))
+        grads, total = clip_grad_norm(grads, cfg.get('grad_clip', 2.0))
+        if out is not None:
+            out['grad_norm'] = total
     if state is None:
         state = {'t': 0, 'm': {n: torch.zeros_like(leaves[n]) for n, _, _ in names}, 'v': {n: torch.zeros_like(leaves[n]) for n, _, _ in names}}
     t = state['t'] + 1
