@@ -15,6 +15,7 @@
 // S may be a row block of the global matrix (multi-GPU row sharding): row0 is the global index
 // of its first row, and s_gt[] carries the GT score of every caption (gathered over ranks).
 #include "itr_internal.h"
+#include "rank_key.h"
 #include <mutex>
 
 namespace itr {
@@ -30,20 +31,7 @@ __global__ void gather_gt_kernel(const float *__restrict__ S, int64_t ldS, int64
     if (g >= 0 && g < nrows) s_gt[j] = S[g * ldS + j];
 }
 
-// (score, index) as ONE 64-bit key: larger score first, then the larger index -- exactly the tie rule of the counts
-// (#{S_k > S_gt} + #{k > gt : S_k == S_gt} = #{key_k > key_gt}) and of the top-1 (np.argsort(...)[::-1]: the higher index wins).
-// Keys of distinct elements are distinct, so the counts are those of a TOTAL order -- which is what makes i2t cheap: the best of an
-// image's im_div ground-truth captions is the one with the LARGEST key, and  min_g #{key > gkey_g} = #{key > max_g gkey_g}:
-// ONE compare per element instead of im_div.
-// score_key canonicalises first: e + 0.0f folds -0.0 into +0.0 (equal as floats, different bit patterns) and fminf(., inf) maps NaN
-// to +inf: a NaN score sorts as the LARGEST value, like np.argsort (NaN last ascending = first after [::-1]); the float64 kernels use
-// the same rule.
-__device__ __forceinline__ uint32_t score_key(float e) {
-    const uint32_t u = __float_as_uint(fminf(e + 0.0f, INFINITY));
-    return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);      // = float_order_key, as three integer instructions
-}
-__device__ __forceinline__ unsigned long long key64(uint32_t hi, uint32_t lo) { return ((unsigned long long)hi << 32) | lo; }
-__device__ __forceinline__ unsigned long long rank_key(float e, unsigned idx) { return key64(score_key(e), idx); }
+// The order key of the counts and the top-1 (score_key, rank_key): rank_key.h, shared with the top-K lists (topk.hip).
 
 // ---- ONE pass over S for both directions (round 5) ----------------------------------------------------------
 // Rounds 1-4 read the score matrix twice (a row pass for i2t, a column pass for t2i: 1.0 GB for the 0.5 GB matrix of 5k x 25k,
@@ -290,12 +278,7 @@ static int rank_resident_slots(int64_t *slots) {
 // index, so t2i's top-1 takes a second pass: max key per column first, then the highest row
 // holding it.
 constexpr int T2I_ROWS = 128;      // image rows per workgroup of the float64 column pass
-// canon_f64: -0.0 -> +0.0 and NaN -> +inf (the fp32 kernels' rule, np.argsort's order); applied to every score the kernels load
-__device__ __forceinline__ double canon_f64(double d) { return fmin(d + 0.0, (double)INFINITY); }
-__device__ __forceinline__ unsigned long long double_order_key(double d) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
+// canon_f64 / double_order_key: rank_key.h
 
 __global__ void gather_gt_f64_kernel(const double *__restrict__ S, int64_t ldS, int64_t row0, int64_t nrows,
                                      int64_t Nc, int im_div, double *__restrict__ s_gt) {

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libitr_hip.so")
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 i32, i64, f32, vp, sz, u64 = C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_uint64
 
@@ -105,6 +105,10 @@ SIGNATURES = {
     "itr_rank_counts_f64": (i32, [vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp]),
     "itr_rank_t2i_top1_f64": (i32, [vp, i64, i64, i64, i64, vp, vp, vp]),
     "itr_recall_from_ranks": (i32, [vp, i64, vp]),
+    "itr_topk_workspace_bytes": (sz, [i64, i64, i32]),
+    "itr_topk": (i32, [vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "itr_topk_merge": (i32, [vp, vp, i32, i64, i32, i32, vp, vp, vp]),
+    "itr_topk_f64": (i32, [vp, i64, i64, i64, i32, vp, vp, vp, vp, vp]),
     # ---- training step
     "itr_l2norm_fwd_save": (i32, [vp, vp, vp, i64, i32, f32, vp]),
     "itr_l2norm_bwd": (i32, [vp, vp, vp, vp, i64, i32, f32, vp]),

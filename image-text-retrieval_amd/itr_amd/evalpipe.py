@@ -245,6 +245,33 @@ def finalize_ranks(comm, S_local, row0, n_img_total, im_div=5, rank_fn=None, gat
 _IMG_ALIGN = 4  # the SCAN kernel works on 4 images per workgroup
 
 
+def finalize_topk(comm, S_local, row0, n_img_total, k, topk_fn=None, merge_fn=None):
+    """The top-k lists of the row-sharded matrix (evaluation.topk on the whole of it).  Row lists are local and gathered
+    like finalize_ranks' rank vectors; every rank's partial column lists (its rows only) are all-gathered and merged, which
+    gives the whole-matrix lists for every partition (the order is one total order on (score, index) keys).
+    Returns host arrays (i2t_idx int64 [Ni, k], i2t_val [Ni, k], t2i_idx int64 [Nc, k], t2i_val [Nc, k]).
+    topk_fn / merge_fn default to the HIP kernels (ops.topk_lists / ops.topk_merge_cols); the gloo CPU tests inject
+    reference versions."""
+    topk_fn = topk_fn or ops.topk_lists
+    merge_fn = merge_fn or ops.topk_merge_cols
+    Nc = S_local.shape[1]
+    r_idx, r_val, part = topk_fn(S_local, k, row0)
+    if comm.on:
+        counts = [block_range(n_img_total, comm.world, q, _IMG_ALIGN)[1] - block_range(n_img_total, comm.world, q, _IMG_ALIGN)[0]
+                  for q in range(comm.world)]
+        ib, maxrows = comm.all_gather_rows(r_idx, counts)
+        vb, _ = comm.all_gather_rows(r_val, counts)
+        r_idx = torch.cat([ib[q * maxrows:q * maxrows + counts[q]] for q in range(comm.world)], 0)
+        r_val = torch.cat([vb[q * maxrows:q * maxrows + counts[q]] for q in range(comm.world)], 0)
+        kb, _ = comm.all_gather_rows(part[0].contiguous(), [Nc] * comm.world)
+        pb, _ = comm.all_gather_rows(part[1].contiguous(), [Nc] * comm.world)
+        parts = [(kb[q * Nc:(q + 1) * Nc], pb[q * Nc:(q + 1) * Nc]) for q in range(comm.world)]
+    else:
+        parts = [part]
+    c_idx, c_val = merge_fn(parts, k)
+    return (r_idx.cpu().numpy().astype(np.int64), r_val.cpu().numpy(), c_idx.cpu().numpy().astype(np.int64), c_val.cpu().numpy())
+
+
 class GruModelEval:
     """Sharded evaluation of the GRU model family (SCAN; VSE++ pooled cosine) on packed inputs."""
 
@@ -718,7 +745,7 @@ class _FeatureBlocks:
             self.consumed[k & 1] = cur.record_event()      # the consumer has queued its work on this block
 
 
-def evaluate_precomp(model, dataset, comm=None, fold=None, batch=4096, block_rows=640):
+def evaluate_precomp(model, dataset, comm=None, fold=None, batch=4096, block_rows=640, topk=0):
     """Recall ranks of `model` on a PrecompDataset (datamodule.data_loader), one process per GPU.
 
     Unlike encode_data + cal_sims (the reference-shaped path: 5 x redundant image encodes, host numpy arrays, a Python
@@ -726,7 +753,8 @@ def evaluate_precomp(model, dataset, comm=None, fold=None, batch=4096, block_row
     axis is sharded over ranks and exchanged with ONE all-gather, and the row block of the similarity matrix is scored
     by the fused kernels.  fold = (k, size) restricts to captions [k*size, (k+1)*size) (MS-COCO 1k folds,
     evaluation.py:296-300).  block_rows: images per streamed feature block of the word-level models (see _FeatureBlocks).
-    Returns (i2t_rank, i2t_top1, t2i_rank, t2i_top1) as host int64 arrays."""
+    Returns (i2t_rank, i2t_top1, t2i_rank, t2i_top1) as host int64 arrays; with topk > 0 the pair (those ranks, the top-k lists
+    of finalize_topk)."""
     comm = comm or Comm()
     if comm.virtual:
         raise ValueError("evaluate_precomp: the virtual caption split is a test hook of the resident-input path (bench.py --virtual-split)")
@@ -807,11 +835,12 @@ def evaluate_precomp(model, dataset, comm=None, fold=None, batch=4096, block_row
                 else:
                     raise ValueError("unknown measure:", cfg.get('measure'))
                 S = exchange_score(comm, img, send, ranges, n_cap, fn)
-                return finalize_ranks(comm, S, i0, n_img, im_div)
+                ranks = finalize_ranks(comm, S, i0, n_img, im_div)
+                return (ranks, finalize_topk(comm, S, i0, n_img, topk)) if topk > 0 else ranks
             sw = {k: v.detach() for k, v in model.sim_enc.state_dict().items()} if name == 'SGRAF' else None
-            _, ranks, _ = ev.scan_eval(feats, toks, off, lens_sorted, order, n_img, n_cap, im_div, sgraf_weights=sw, cap_ranges=ranges,
+            S, ranks, _ = ev.scan_eval(feats, toks, off, lens_sorted, order, n_img, n_cap, im_div, sgraf_weights=sw, cap_ranges=ranges,
                                        all_lengths=lens_all)
-            return ranks
+            return (ranks, finalize_topk(comm, S, i0, n_img, topk)) if topk > 0 else ranks
         # ---- BERT models: one vector per caption
         if name not in ('SAEM', 'CAMERA'):
             raise NotImplementedError("evaluate_precomp: model %r" % name)
@@ -828,5 +857,5 @@ def evaluate_precomp(model, dataset, comm=None, fold=None, batch=4096, block_row
         if name == 'CAMERA':
             boxes = _features_to_device(dataset.boxes, img_lo + i0, img_lo + i1, dev)
             wh = _features_to_device(dataset.img_wh, img_lo + i0, img_lo + i1, dev)
-        _, ranks = pe.eval(feats, boxes, wh, None, None, None, lens_b, n_img, n_cap, im_div, cap_emb=cap)
-        return ranks
+        S, ranks = pe.eval(feats, boxes, wh, None, None, None, lens_b, n_img, n_cap, im_div, cap_emb=cap)
+        return (ranks, finalize_topk(comm, S, i0, n_img, topk)) if topk > 0 else ranks

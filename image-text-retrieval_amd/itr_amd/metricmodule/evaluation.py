@@ -137,21 +137,25 @@ def cal_sims(model, img_embs, cap_embs, lengths=None, shard_size=128, ref_quirk_
     return d
 
 
+def _device_matrix(sims):
+    """numpy array or tensor -> contiguous device tensor: float32 stays float32, anything else becomes float64."""
+    if torch.is_tensor(sims):
+        S = sims.detach()
+        if S.dtype not in (torch.float32, torch.float64):
+            S = S.to(torch.float64)
+        return S.contiguous().cuda()
+    a = np.asarray(sims)
+    if a.dtype != np.float32:
+        a = a.astype(np.float64, copy=False)
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
 def _ranks(sims):
     """Rank vectors of a similarity matrix in the arithmetic the caller holds it in: float64 input (cal_sims' output,
     an ensemble average -- what the reference argsorts, evaluation.py:169, :209, :380) is counted in float64, so the
     indices equal the reference's even where two scores differ by less than an fp32 ulp; float32 input is counted in
     float32; anything else is widened to float64 (exact for every narrower type)."""
-    if torch.is_tensor(sims):
-        S = sims.detach()
-        if S.dtype not in (torch.float32, torch.float64):
-            S = S.to(torch.float64)
-        S = S.contiguous().cuda()
-    else:
-        a = np.asarray(sims)
-        if a.dtype != np.float32:
-            a = a.astype(np.float64, copy=False)
-        S = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    S = _device_matrix(sims)
     if S.dtype == torch.float64:
         i_rank, i_top, t_rank, t_top = ops.rank_counts_f64(S, 5)
     else:
@@ -159,6 +163,27 @@ def _ranks(sims):
         t_top = t_best & 0xffffffff
     return (i_rank.cpu().numpy().astype(np.float64), i_top.cpu().numpy().astype(np.float64),
             t_rank.cpu().numpy().astype(np.float64), t_top.cpu().numpy().astype(np.float64))
+
+
+def topk(sims, k=10):
+    """The first k entries of the reference's ranked lists inds = np.argsort(sims[index])[::-1] (evaluation.py:169 for i2t,
+    :209 for t2i), selected on the GPU in the arithmetic the caller holds the matrix in (as _ranks: float64 input is selected
+    in float64).  Order: larger score first, the higher index on exact ties, -0.0 == +0.0, NaN as +inf (column 0 is the
+    ranker's top1).  -> {'i2t_topk': int64 (Ni, k), 'i2t_topk_scores': (Ni, k), 't2i_topk': int64 (Nc, k),
+    't2i_topk_scores': (Nc, k)}, scores in the matrix's dtype with their original bits."""
+    S = _device_matrix(sims)
+    r_idx, r_val, part = ops.topk_lists(S, k)
+    c_idx, c_val = ops.topk_merge_cols([part], k)
+    return {'i2t_topk': r_idx.cpu().numpy().astype(np.int64), 'i2t_topk_scores': r_val.cpu().numpy(),
+            't2i_topk': c_idx.cpu().numpy().astype(np.int64), 't2i_topk_scores': c_val.cpu().numpy()}
+
+
+def _save_topk(save_dir, data_name, tag, k, lists):
+    """`<save_dir>/<data_name>_<tag>_top<k>.npz` next to the result YAML (fold5: PART_<i>_-prefixed arrays)."""
+    import os
+    path = os.path.join(save_dir, f'{data_name}_{tag}_top{k}.npz')
+    np.savez(path, **lists)
+    return path
 
 
 def i2t(sims, return_ranks=False):
@@ -250,9 +275,10 @@ def _load_for_eval(model_path, data_path):
     return model, _config
 
 
-def _score_blocks(models_embs, fold5):
+def _score_blocks(models_embs, fold5, k=0, lists=None):
     """models_embs: list of (model, img_embs, cap_embs, cap_lens, shard_size); the similarity matrices of the
-    models are averaged (ensemble, evaluation.py:377-381)."""
+    models are averaged (ensemble, evaluation.py:377-381).  k > 0: the top-k lists of every (float64) matrix go into
+    `lists` (fold5: keys PART_<i>_..., indices local to the part's matrix)."""
     def sims_of(sl_img, sl_cap):
         acc = None
         for model, img, cap, lens, shard in models_embs:
@@ -262,18 +288,24 @@ def _score_blocks(models_embs, fold5):
 
     n = len(models_embs[0][1])
     if not fold5:
-        return cal_recall(sims_of(slice(0, n, 5), slice(None)))
+        sims = sims_of(slice(0, n, 5), slice(None))
+        if k > 0:
+            lists.update(topk(sims, k))
+        return cal_recall(sims)
     res_dic = {'sum_result': []}
     for i in range(5):
         print(f"--------------------- The {i + 1} part ---------------------")
-        part = cal_recall(sims_of(slice(i * 5000, (i + 1) * 5000, 5), slice(i * 5000, (i + 1) * 5000)))
+        sims = sims_of(slice(i * 5000, (i + 1) * 5000, 5), slice(i * 5000, (i + 1) * 5000))
+        if k > 0:
+            lists.update({f'PART_{i + 1}_{key}': v for key, v in topk(sims, k).items()})
+        part = cal_recall(sims)
         res_dic[f'PART_{i + 1}'] = part
         res_dic['sum_result'] += part['result']
     res_dic['Mean_metrics'] = _mean_metrics(res_dic)
     return res_dic
 
 
-def _evalrank(model_paths, data_path, split, fold5, tag):
+def _evalrank(model_paths, data_path, split, fold5, tag, topk=0):
     import os
     import yaml
     from ..datamodule import data_loader as data
@@ -290,7 +322,8 @@ def _evalrank(model_paths, data_path, split, fold5, tag):
         img, cap, lens = encode_data(model, data_loader, islength=islength)
         embs.append((model, img, cap, lens, cfg['batch_size'] * 5))
     print('#Images: %d, #Captions: %d' % (embs[0][1].shape[0] / 5, embs[0][2].shape[0]))
-    res_dic = _score_blocks(embs, fold5)
+    lists = {}
+    res_dic = _score_blocks(embs, fold5, topk, lists)
     res_dic['data_name'] = _config['data_name'] + ('_5fold' if fold5 else '')
     if len(model_paths) > 1 and fold5:
         res_dic['modal_path_1'], res_dic['modal_path_2'] = model_paths[0], model_paths[1]
@@ -298,6 +331,8 @@ def _evalrank(model_paths, data_path, split, fold5, tag):
     out_file = os.path.join(save_dir, f'{res_dic["data_name"]}_{tag}_result.yaml')
     with open(out_file, 'w') as yaml_file:
         yaml.safe_dump(_plain(res_dic), yaml_file)
+    if topk > 0:
+        _save_topk(save_dir, res_dic['data_name'], tag, topk, lists)
     return res_dic
 
 
@@ -313,10 +348,11 @@ def _recall_dict(ranks):
             't2i_top1': t_top}
 
 
-def evalrank_fast(model_path, data_path=None, split='dev', fold5=False, comm=None):
+def evalrank_fast(model_path, data_path=None, split='dev', fold5=False, comm=None, topk=0):
     """Same result dict / YAML as evalrank_single through the sharded device-resident pipeline
     (itr_amd.evalpipe.evaluate_precomp): launch one process per GPU with torch.distributed.run; rank 0 writes
-    `<run dir>/<data_name>[_5fold]_single_result.yaml`."""
+    `<run dir>/<data_name>[_5fold]_single_result.yaml`, and with topk > 0 also `..._single_top<topk>.npz` (the top-k lists of
+    the fp32 matrix the pipeline ranks; evalpipe.finalize_topk)."""
     import os
     import yaml
     from .. import evalpipe
@@ -324,12 +360,20 @@ def evalrank_fast(model_path, data_path=None, split='dev', fold5=False, comm=Non
     model, _config = _load_for_eval(model_path, data_path)
     dset = data.PrecompDataset(os.path.join(_config['data_path'], _config['data_name']), split, _config)
     comm = comm or evalpipe.Comm()
+    lists = {}
+
+    def run(fold, prefix):
+        if topk <= 0:
+            return evalpipe.evaluate_precomp(model, dset, comm, fold=fold)
+        ranks, tl = evalpipe.evaluate_precomp(model, dset, comm, fold=fold, topk=topk)
+        lists.update({prefix + key: v for key, v in zip(('i2t_topk', 'i2t_topk_scores', 't2i_topk', 't2i_topk_scores'), tl)})
+        return ranks
     if not fold5:
-        res_dic = _recall_dict(evalpipe.evaluate_precomp(model, dset, comm))
+        res_dic = _recall_dict(run(None, ''))
     else:
         res_dic = {'sum_result': []}
         for i in range(5):
-            part = _recall_dict(evalpipe.evaluate_precomp(model, dset, comm, fold=(i, 5000)))
+            part = _recall_dict(run((i, 5000), f'PART_{i + 1}_'))
             res_dic[f'PART_{i + 1}'] = part
             res_dic['sum_result'] += part['result']
         res_dic['Mean_metrics'] = _mean_metrics(res_dic)
@@ -337,14 +381,17 @@ def evalrank_fast(model_path, data_path=None, split='dev', fold5=False, comm=Non
     if comm.rank == 0:
         with open(os.path.join(os.path.dirname(model_path), f'{res_dic["data_name"]}_single_result.yaml'), 'w') as f:
             yaml.safe_dump(_plain(res_dic), f)
+        if topk > 0:
+            _save_topk(os.path.dirname(model_path), res_dic['data_name'], 'single', topk, lists)
     return res_dic
 
 
-def evalrank_single(model_path, data_path=None, split='dev', fold5=False):
-    """evaluation.py:262-335."""
-    return _evalrank([model_path], data_path, split, fold5, 'single')
+def evalrank_single(model_path, data_path=None, split='dev', fold5=False, topk=0):
+    """evaluation.py:262-335.  topk > 0: also `<data_name>[_5fold]_single_top<topk>.npz` next to the YAML (`topk`)."""
+    return _evalrank([model_path], data_path, split, fold5, 'single', topk)
 
 
-def evalrank_ensemble(model_path, model_path2, data_path=None, split='dev', fold5=False):
-    """evaluation.py:338-435: the two models' similarity matrices are averaged before ranking."""
-    return _evalrank([model_path, model_path2], data_path, split, fold5, 'ensemble')
+def evalrank_ensemble(model_path, model_path2, data_path=None, split='dev', fold5=False, topk=0):
+    """evaluation.py:338-435: the two models' similarity matrices are averaged before ranking.  topk > 0: the top-k lists
+    of the float64 average go to `<data_name>[_5fold]_ensemble_top<topk>.npz`."""
+    return _evalrank([model_path, model_path2], data_path, split, fold5, 'ensemble', topk)

@@ -1034,3 +1034,79 @@ def recall_from_ranks(ranks):
     out = (C.c_double * 5)()
     _lib.check(lib.itr_recall_from_ranks(r.ctypes.data_as(C.c_void_p), len(r), out))
     return tuple(float(v) for v in out)
+
+
+# ------------------------------------------------------------------------------------------
+TOPK_MAX = 128         # ITR_TOPK_MAX (include/itr_hip.h)
+TOPK_MAX_PARTS = 32    # ITR_TOPK_MAX_PARTS
+
+
+def topk_lists(S, k, row0=0, rows=True, cols=True):
+    """The first k entries of every row's and every column's ranked list (inds = np.argsort(...)[::-1],
+    evaluation.py:169, :209) in the ranker's order: larger score first, the higher index on exact ties, -0.0 == +0.0,
+    NaN as +inf.  Scores are returned with their original bits.  S: a (row block of a) similarity matrix holding global
+    rows row0 .. row0 + n - 1; any row stride and alignment.
+    -> (row_idx int32 [n, k], row_val [n, k], col_part), None for a direction not asked for.
+    fp32: col_part = (key int64 [Nc, k], val float32 [Nc, k]), this block's partial column lists (key = ordered score << 32 |
+    global row; key 0 = empty entry); `topk_merge_cols` merges the parts of several blocks / ranks into the whole-matrix lists.
+    float64 (whole matrices only, row0 = 0): col_part = (col_idx int32 [Nc, k], col_val float64 [Nc, k]), already final."""
+    lib = _lib.load()
+    if not torch.is_tensor(S):
+        raise TypeError("S must be a torch tensor")
+    f64 = S.dtype == torch.float64
+    if S.dim() != 2:
+        raise ValueError("topk_lists: S must be 2-D, got shape %s" % (tuple(S.shape),))
+    S_ = _dev_view(S, torch.float64 if f64 else torch.float32)
+    n, Nc = S_.shape
+    dev = S_.device
+    k = int(k)
+    vdt = S_.dtype
+    row_idx = torch.empty(n, k, device=dev, dtype=torch.int32) if rows else None
+    row_val = torch.empty(n, k, device=dev, dtype=vdt) if rows else None
+    if f64:
+        if row0 != 0:
+            raise ValueError("topk_lists: a float64 matrix is selected whole (row0 = 0)")
+        col_idx = torch.empty(Nc, k, device=dev, dtype=torch.int32) if cols else None
+        col_val = torch.empty(Nc, k, device=dev, dtype=vdt) if cols else None
+        _lib.check(lib.itr_topk_f64(_p(S_), S_.stride(0), n, Nc, k, _p(row_idx), _p(row_val), _p(col_idx), _p(col_val), _stream()))
+        return row_idx, row_val, ((col_idx, col_val) if cols else None)
+    col_key = (torch.zeros if n == 0 else torch.empty)(Nc, k, device=dev, dtype=torch.int64) if cols else None
+    col_val = (torch.zeros if n == 0 else torch.empty)(Nc, k, device=dev, dtype=vdt) if cols else None
+    wsb = lib.itr_topk_workspace_bytes(n, Nc, k)
+    ws = torch.empty(wsb // 8 + 1, device=dev, dtype=torch.int64) if wsb else None
+    _lib.check(lib.itr_topk(_p(S_), S_.stride(0), int(row0), n, Nc, k, _p(row_idx), _p(row_val), _p(col_key), _p(col_val), _p(ws), wsb,
+                            _stream()))
+    return row_idx, row_val, ((col_key, col_val) if cols else None)
+
+
+def _dev_view(t, dtype):
+    """Like _dev, but keeps a row-strided view (the kernels take ldS): no copy of a column slice of a larger matrix."""
+    if not t.is_cuda:
+        raise RuntimeError("S is on %s: the itr_amd ops only run on the GPU (no CPU fallback)" % t.device)
+    if t.dtype != dtype:
+        raise TypeError("S must be %s, got %s" % (dtype, t.dtype))
+    if t.stride(1) != 1 or t.stride(0) < max(t.shape[1], 1):
+        t = t.contiguous()
+    return t
+
+
+def topk_merge_cols(parts, k):
+    """Merge the column parts of `topk_lists` (row blocks of one matrix, or ranks) into the whole-matrix lists
+    -> (col_idx int32 [Nc, k] global rows, col_val [Nc, k]).  Equal to the lists of the whole matrix for every partition of
+    its rows.  A float64 part is already final: one part, cut to k."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("topk_merge_cols: no parts")
+    if parts[0][1].dtype == torch.float64:
+        if len(parts) != 1 or parts[0][0].shape[1] < k:
+            raise ValueError("topk_merge_cols: a float64 matrix is selected whole: one part with >= k entries per column")
+        idx, val = parts[0]
+        return idx[:, :k].contiguous(), val[:, :k].contiguous()
+    lib = _lib.load()
+    keys = torch.stack([_dev(p[0], torch.int64, "part key") for p in parts], 0).contiguous()
+    vals = torch.stack([_dev(p[1], torch.float32, "part val") for p in parts], 0).contiguous()
+    P, Nc, k_in = keys.shape
+    col_idx = torch.empty(Nc, int(k), device=keys.device, dtype=torch.int32)
+    col_val = torch.empty(Nc, int(k), device=keys.device, dtype=torch.float32)
+    _lib.check(lib.itr_topk_merge(_p(keys), _p(vals), P, Nc, k_in, int(k), _p(col_idx), _p(col_val), _stream()))
+    return col_idx, col_val

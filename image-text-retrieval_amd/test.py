@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Evaluate checkpoints like the reference's test.py:  python test.py MODEL_PATH [MODEL_PATH_2] [--data-path P]
-[--split test|testall|dev] [--fold5]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml"""
+[--split test|testall|dev] [--fold5] [--topk K]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
+(and with --topk K the top-K retrieval lists of every query in <data_name>[_5fold]_{single,ensemble}_top<K>.npz)"""
 import argparse
 import os
 import sys
@@ -16,6 +17,8 @@ if __name__ == "__main__":
     ap.add_argument("--fold5", action="store_true")
     ap.add_argument("--fast", action="store_true",
                     help="sharded device-resident evaluation (evalpipe.evaluate_precomp); run under torch.distributed.run for >1 GPU")
+    ap.add_argument("--topk", type=int, default=0, metavar="K",
+                    help="also write the top-K retrieved items of every query (indices and scores) to <data_name>..._top<K>.npz")
     a = ap.parse_args()
     if a.fast:
         import torch
@@ -24,10 +27,11 @@ if __name__ == "__main__":
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             dist.init_process_group("nccl")
-        evaluation.evalrank_fast(a.model_path[0], data_path=a.data_path, split=a.split, fold5=a.fold5)
+        evaluation.evalrank_fast(a.model_path[0], data_path=a.data_path, split=a.split, fold5=a.fold5, topk=a.topk)
         if dist.is_initialized():
             dist.destroy_process_group()
     elif len(a.model_path) == 1:
-        evaluation.evalrank_single(a.model_path[0], data_path=a.data_path, split=a.split, fold5=a.fold5)
+        evaluation.evalrank_single(a.model_path[0], data_path=a.data_path, split=a.split, fold5=a.fold5, topk=a.topk)
     else:
-        evaluation.evalrank_ensemble(a.model_path[0], a.model_path[1], data_path=a.data_path, split=a.split, fold5=a.fold5)
+        evaluation.evalrank_ensemble(a.model_path[0], a.model_path[1], data_path=a.data_path, split=a.split, fold5=a.fold5,
+                                     topk=a.topk)

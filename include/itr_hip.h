@@ -367,6 +367,35 @@ int itr_rank_t2i_top1_f64(const double *S, int64_t ldS, int64_t row0, int64_t n_
 /* host-side summary (evaluation.py:181-185): out5 = r1, r5, r10, medr, meanr. */
 int itr_recall_from_ranks(const int32_t *ranks_host, int64_t n, double *out5);
 
+/* ---- top-K retrieval lists (itr/metricmodule/evaluation.py:156-222) ----------------------
+ * The reference builds the full ranked list of every query, inds = np.argsort(sims[index])[::-1] (evaluation.py:169 i2t,
+ * :209 t2i), and keeps inds[0] and the ground truth's position.  These entry points return the first K entries of those
+ * lists, selected on the GPU in the ranker's order (larger score first, the higher index on exact ties, -0.0 == +0.0, NaN
+ * as +inf): column 0 is the ranker's top-1.  Returned scores are the ORIGINAL bits of S at the returned index (a -0.0
+ * stays -0.0, a NaN stays NaN).  1 <= K <= ITR_TOPK_MAX (ITR_ERR_UNSUPPORTED above).
+ * itr_topk: S is the LOCAL row block [n_rows_local, Nc] (leading dimension ldS >= Nc, any alignment) holding global rows
+ * row0 .. row0 + n_rows_local - 1.  Either direction may be left out by passing NULL for both of its outputs.
+ *   i2t: row_idx [n_rows_local, K] (column indices, best first), row_val [n_rows_local, K]; K > Nc -> ITR_ERR_BADARG.
+ *   t2i: col_key [Nc, K] (uint64 key = ordered score << 32 | GLOBAL row, best first) and col_val [Nc, K]: a partial list of
+ *        this block's rows.  A block with fewer than K rows leaves key 0 / score 0 in the entries past them.
+ *        itr_topk_merge merges n_parts such lists, laid out [n_parts][Nc][K_in] (row blocks of one matrix, ranks), into the
+ *        whole-matrix lists col_idx [Nc, K] (global rows; -1 where the parts hold fewer than K entries) / col_val [Nc, K];
+ *        the result is the same for every partition of the rows.  n_parts <= ITR_TOPK_MAX_PARTS, K <= n_parts * K_in.
+ *   workspace: itr_topk_workspace_bytes(n_rows_local, Nc, K) bytes, 8-byte aligned (0 bytes: may be NULL).
+ * itr_topk_f64: a whole float64 matrix (cal_sims' output, ensemble averages); the key is the ordered double, then the index,
+ * with the same tie, NaN and signed-zero rules.  col_idx [Nc, K] / col_val [Nc, K] are final; K larger than a requested
+ * line -> ITR_ERR_BADARG.
+ * n_rows == 0 or Nc == 0: ITR_OK, nothing written. */
+#define ITR_TOPK_MAX 128
+#define ITR_TOPK_MAX_PARTS 32
+size_t itr_topk_workspace_bytes(int64_t n_rows_local, int64_t Nc, int K);
+int itr_topk(const float *S, int64_t ldS, int64_t row0, int64_t n_rows_local, int64_t Nc, int K, int32_t *row_idx,
+             float *row_val, uint64_t *col_key, float *col_val, void *workspace, size_t workspace_bytes, itr_stream_t stream);
+int itr_topk_merge(const uint64_t *part_key, const float *part_val, int n_parts, int64_t Nc, int K_in, int K,
+                   int32_t *col_idx, float *col_val, itr_stream_t stream);
+int itr_topk_f64(const double *S, int64_t ldS, int64_t n_rows, int64_t Nc, int K, int32_t *row_idx, double *row_val,
+                 int32_t *col_idx, double *col_val, itr_stream_t stream);
+
 /* ---- a14: the training step  model.train_emb (itr/modalmodule/Models.py:198-225, :115-145): forward -> loss ->
  * backward -> clip_grad_norm_(2.0) -> Adam.  Backward contractions are itr_gemm_nt on transposed operands;
  * these are the pieces around them. ------------------------------------------------------------------------- */
