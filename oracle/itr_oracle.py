@@ -61,27 +61,33 @@ def encoder_image_precomp(images, fc_weight, fc_bias, no_imgnorm=False, use_abs=
 # --------------------------------------------------------------------------------------
 
 
-def rs_gcn(w, p, v):
+def rs_gcn(w, p, v, bn_stats=False):
     """Rs_GCN.forward on v (B, N, D) (the reference works on the (B, D, N) transpose; a Conv1d with kernel size 1 is a
-    Linear over the channel axis): R = theta(v) phi(v)^T / N, y = R g(v), v* = BN(W y) + v  (vsrn_.py:50-71)."""
+    Linear over the channel axis): R = theta(v) phi(v)^T / N, y = R g(v), v* = BN(W y) + v  (vsrn_.py:50-71).
+    bn_stats: False (evaluation-mode BatchNorm), or None / a list for training mode (_bn_train: batch statistics over B x N)."""
     def conv(name, x):
         return x @ w[p + name + '.weight'][:, :, 0].t() + w[p + name + '.bias']
     g_v, theta_v, phi_v = conv('g', v), conv('theta', v), conv('phi', v)
     R = theta_v @ phi_v.transpose(1, 2)
     y = (R / R.shape[-1]) @ g_v
     wy = conv('W.0', y)
-    return _bn_eval(wy, w, p + 'W.1', channel_dim=2) + v
+    if bn_stats is False:
+        return _bn_eval(wy, w, p + 'W.1', channel_dim=2) + v
+    return _bn_train(wy, w, p + 'W.1', channel_dim=2, bn_stats=bn_stats) + v
 
 
-def vsrn_image(w, images, data_name='coco_precomp', no_imgnorm=False, use_abs=False):
+def vsrn_image(w, images, data_name='coco_precomp', no_imgnorm=False, use_abs=False, bn_stats=False):
     """EncoderImagePrecompAttn.forward (ImgEncoder.py:199-231) -> (features (B, D), GCN_img_emd (B, N, D)).
     NB both l2norm calls on the region tensors use the reference's DEFAULT dim=1: they normalise ACROSS the regions
-    (utils.py:11), not across the features -- restated as written."""
+    (utils.py:11), not across the features -- restated as written.
+    bn_stats: False (evaluation mode), or None / a list for the GCN BatchNorms in training mode (rs_gcn; coco only)."""
+    if bn_stats is not False and data_name == 'f30k_precomp':
+        raise NotImplementedError("training-mode f30k image BatchNorm")
     x = images @ w['fc.weight'].t() + w['fc.bias']
     if data_name != 'f30k_precomp':
         x = l2norm(x, dim=1)
     for i in (1, 2, 3, 4):
-        x = rs_gcn(w, 'Rs_GCN_%d.' % i, x)
+        x = rs_gcn(w, 'Rs_GCN_%d.' % i, x, bn_stats)
     gcn = l2norm(x, dim=1)
     B, N, _ = gcn.shape
     seq = gru_direction(gcn, [N] * B, w['img_rnn.weight_ih_l0'], w['img_rnn.weight_hh_l0'], w['img_rnn.bias_ih_l0'],
@@ -468,6 +474,96 @@ def sgraf_model_train_grads(wi, wt, ws, images, ids, lengths, cfg, out=None):
         grads, total = clip_grad_norm(grads, cfg.get('grad_clip', 2.0))
     if out is not None:
         out.update(scores=sims.detach(), grad_norm=total, bn_stats=bn_stats)
+    return loss.detach(), {n: g for (n, _, _), g in zip(names, grads)}
+
+
+# --------------------------------------------------------------------------------------
+# VSRN training step: image tower with training-mode GCN BatchNorms, last-state text GRU, cosine hinge, and the captioning
+# branch S2VTAttModel = EncoderRNN + attention DecoderRNN under LanguageModelCriterion (Models.py:303-365,
+# Fusionmodule.py:10-365, Objectives.py:138-158).  Dropout is identity (the tests run every dropout at p = 0).
+# Pinned by G21 = the reference's own VSRN.train_emb: both losses and every clipped gradient (tests/test_oracle_golden.py).
+# --------------------------------------------------------------------------------------
+
+
+def _gru_cell(x, h, w_ih, w_hh, b_ih, b_hh):
+    """One torch.nn.GRU step from hidden state h (gate order r, z, n; see gru_direction)."""
+    H = w_hh.shape[1]
+    gi = x @ w_ih.t() + b_ih
+    gh = h @ w_hh.t() + b_hh
+    r = torch.sigmoid(gi[:, :H] + gh[:, :H])
+    z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+    n = torch.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+    return (1.0 - z) * n + z * h
+
+
+def vsrn_attention(w, hidden, enc_out):
+    """Attention.forward (Fusionmodule.py:130-145), literally: linear1 over cat(encoder_outputs, hidden repeated over the regions)
+    at every call, tanh, linear2 (no bias), softmax over the regions, context = alpha @ encoder_outputs."""
+    B, N, H = enc_out.shape
+    inputs = torch.cat((enc_out, hidden.unsqueeze(1).repeat(1, N, 1)), 2).view(-1, 2 * H)
+    o = torch.tanh(inputs @ w['decoder.attention.linear1.weight'].t() + w['decoder.attention.linear1.bias']) \
+        @ w['decoder.attention.linear2.weight'].t()
+    alpha = torch.softmax(o.view(B, N), dim=1)
+    return torch.bmm(alpha.unsqueeze(1), enc_out).squeeze(1)
+
+
+def vsrn_caption_loss(w, vid_feats, labels, masks, max_len):
+    """LanguageModelCriterion(S2VTAttModel(vid_feats, labels, 'train'), labels[:, 1:], masks[:, 1:]) (Models.py:303-313).
+    w: the caption model's state_dict ('encoder.*', 'decoder.*').  EncoderRNN (Fusionmodule.py:150-203): vid2hid, GRU over the
+    regions; DecoderRNN in 'train' mode (:259-302): hidden starts at the encoder's last state, max_len - 1 teacher-forced steps of
+    attention -> cat(word, context) -> GRU step -> log_softmax(out(h)), each step on its own; NLL masked, summed, / batch size
+    (Objectives.py:138-158)."""
+    B, N, Dv = vid_feats.shape
+    x = (vid_feats.reshape(-1, Dv) @ w['encoder.vid2hid.weight'].t() + w['encoder.vid2hid.bias']).view(B, N, -1)
+    enc_out = gru_direction(x, [N] * B, w['encoder.rnn.weight_ih_l0'], w['encoder.rnn.weight_hh_l0'], w['encoder.rnn.bias_ih_l0'],
+                            w['encoder.rnn.bias_hh_l0'])
+    h = enc_out[:, N - 1]
+    targets_emb = w['decoder.embedding.weight'][labels]
+    seq_logprobs = []
+    for i in range(max_len - 1):
+        context = vsrn_attention(w, h, enc_out)
+        dec_in = torch.cat([targets_emb[:, i, :], context], dim=1)
+        h = _gru_cell(dec_in, h, w['decoder.rnn.weight_ih_l0'], w['decoder.rnn.weight_hh_l0'], w['decoder.rnn.bias_ih_l0'],
+                      w['decoder.rnn.bias_hh_l0'])
+        seq_logprobs.append(torch.log_softmax(h @ w['decoder.out.weight'].t() + w['decoder.out.bias'], dim=1).unsqueeze(1))
+    logits = torch.cat(seq_logprobs, 1)
+    target, mask = labels[:, 1:][:, :logits.shape[1]], masks[:, 1:][:, :logits.shape[1]]
+    logits = logits.contiguous().view(-1, logits.shape[2])
+    nll = -logits.gather(1, target.contiguous().view(-1, 1)).squeeze(1)
+    return torch.sum(nll * mask.contiguous().view(-1).to(nll.dtype)) / B
+
+
+def vsrn_model_train_grads(wi, wt, wc, images, ids, lengths, masks, cfg, out=None):
+    """One VSRN.train_emb step up to the clipped gradients (Models.py:343-365): vsrn_image with training-mode GCN BatchNorms ->
+    last-state GRU text tower -> cosine hinge, + vsrn_caption_loss on the GCN region features -> backward -> clip_grad_norm_.
+    wi: EncoderImagePrecompAttn state_dict (parameters and BatchNorm buffers); wt: EncoderText state_dict (one direction);
+    wc: S2VTAttModel state_dict.  Returns (loss, {name: clipped gradient}) with names 'txt.<k>' / 'img.<k>' / 'cap.<k>', in the
+    reference's parameter order txt_enc, img_enc, caption_model (Models.py:295-297).
+    out: None, or a dict that receives 'scores', 'grad_norm' (before clipping), 'bn_stats' (the GCN BatchNorms' batch statistics in
+    call order, _bn_train; names as in wi), 'loss_caption' and 'loss_retrieval'."""
+    is_param = lambda k: not (k.endswith('running_mean') or k.endswith('running_var') or k.endswith('num_batches_tracked'))
+    names = [('txt.' + k, wt, k) for k in wt] + [('img.' + k, wi, k) for k in wi if is_param(k)] + [('cap.' + k, wc, k) for k in wc]
+    with torch.enable_grad():
+        leaves = {n: d[k].detach().clone().requires_grad_(True) for n, d, k in names}
+        wi_l = {k: (leaves['img.' + k] if is_param(k) else wi[k]) for k in wi}
+        wt_l = {k: leaves['txt.' + k] for k in wt}
+        wc_l = {k: leaves['cap.' + k] for k in wc}
+        bn_stats = []
+        img, gcn = vsrn_image(wi_l, images, cfg.get('data_name', 'coco_precomp'), cfg.get('no_imgnorm', False), cfg.get('use_abs', False),
+                              bn_stats=bn_stats)
+        cap, _ = encoder_text(ids, lengths, wt_l, False, cfg.get('no_txtnorm', False), cfg.get('use_abs', False), 'VSRN')
+        scores = (order_sim if cfg.get('measure', 'cosine') == 'order' else cosine_sim)(img, cap)
+        loss_retrieval = hinge_loss(scores, cfg.get('margin', 0.2), cfg.get('max_violation', False))
+        loss_caption = vsrn_caption_loss(wc_l, gcn, ids, masks, cfg['max_len'])
+        loss = loss_retrieval + loss_caption
+        loss.backward()
+    grads = [leaves[n].grad if leaves[n].grad is not None else torch.zeros_like(leaves[n]) for n, _, _ in names]
+    total = None
+    if cfg.get('grad_clip', 2.0) > 0:
+        grads, total = clip_grad_norm(grads, cfg.get('grad_clip', 2.0))
+    if out is not None:
+        out.update(scores=scores.detach(), grad_norm=total, bn_stats=bn_stats,
+                   loss_caption=loss_caption.detach(), loss_retrieval=loss_retrieval.detach())
     return loss.detach(), {n: g for (n, _, _), g in zip(names, grads)}
 
 
