@@ -75,6 +75,9 @@ int scan_scores_impl(const float *img, int64_t n_tiles, int64_t Ni, int64_t Nc, 
 __global__ void gram_kernel(const float *__restrict__ X, const int64_t *__restrict__ row_off, const int32_t *__restrict__ row_cnt, int fixed_rows,
                             int D, float *__restrict__ G, const int64_t *__restrict__ g_off, int upper2);
 __global__ void gram_mfma_kernel(const float *__restrict__ X, int rows, int D, float *__restrict__ G, int upper2);
+// row L2 norms (no eps) and the exclusive prefix sum of len^2 (caption Gram offsets): shared with scan_pairs.hip
+__global__ void rownorm_kernel(const float *__restrict__ X, int64_t rows, int D, float *__restrict__ out);
+__global__ void sq_prefix_kernel(const int32_t *__restrict__ len, int64_t n, int64_t *__restrict__ off);
 // ---- sgr_fused.hip: all graph-reasoning steps of a group of captions in one workgroup
 size_t sgr_fused_workspace_bytes(int64_t n_groups, int64_t n_caps, int sgr_step);
 int sgr_fused_prepare(const int32_t *grp_begin, const int32_t *grp_order, int64_t n_groups, int64_t n_caps, const int32_t *cap_len,

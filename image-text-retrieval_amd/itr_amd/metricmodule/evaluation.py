@@ -395,3 +395,133 @@ def evalrank_ensemble(model_path, model_path2, data_path=None, split='dev', fold
     """evaluation.py:338-435: the two models' similarity matrices are averaged before ranking.  topk > 0: the top-k lists
     of the float64 average go to `<data_name>[_5fold]_ensemble_top<topk>.npz`."""
     return _evalrank([model_path, model_path2], data_path, split, fold5, 'ensemble', topk)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Coarse-to-fine retrieval: a cheap model shortlists k candidates per query, the cross-attention model scores only those pairs
+# (ops.scan_candidate_scores) and re-orders the shortlist (ops.rerank_lists).
+def rerank_rank_vector(lists, coarse_ranks, direction, im_div=5):
+    """Rank vector of the RERANKED ranking (host arithmetic, numpy only).  The reranked ranking of a query is its k shortlisted
+    candidates in fine order followed by all other candidates in coarse order; the rank of a query is the best position of a
+    ground-truth candidate in it (evaluation.py:156-222: i2t the best of the image's `im_div` captions, t2i the caption's image).
+    A ground truth inside the shortlist therefore has its position in the reranked list; with none inside, the best ground truth
+    keeps its coarse rank (the k shortlisted and the same others still stand before it).
+    lists: int [n, k] reranked shortlists; coarse_ranks: [n] ranks under the coarse matrix; direction 'i2t' | 't2i'."""
+    lists = np.asarray(lists)
+    n = lists.shape[0]
+    q = np.arange(n)[:, None]
+    if direction == 'i2t':
+        hit = (lists // im_div) == q
+    elif direction == 't2i':
+        hit = lists == (q // im_div)
+    else:
+        raise ValueError("direction must be 'i2t' or 't2i', got %r" % (direction,))
+    inside = hit.any(axis=1)
+    return np.where(inside, hit.argmax(axis=1), np.asarray(coarse_ranks)).astype(np.float64)
+
+
+def rerank(sims_coarse, score_fn, k, im_div=5):
+    """Both directions of coarse-to-fine retrieval on one (n_img, n_cap) coarse matrix (device float32, or anything
+    `_device_matrix` can turn into it): the k-lists of every image (over captions) and of every caption (over images) come from
+    the top-k path, `score_fn(cand, by)` (cand int32 device [n, k]; by = 'image' for lists of caption indices per image, 'caption'
+    for lists of image indices per caption) returns their fine scores [n, k], and ops.rerank_lists re-orders them.
+    -> ((r1, r5, r10, medr, meanr) i2t, the same for t2i, (i2t_ranks, t2i_ranks), lists) with lists = {'i2t_topk', 'i2t_topk_scores',
+    't2i_topk', 't2i_topk_scores'} (the reranked lists and their fine scores) as `topk` lays them out."""
+    k = int(k)
+    if k < 10:
+        raise ValueError("rerank: k = %d < 10: R@10 would not be defined by the shortlist" % k)
+    S = _device_matrix(sims_coarse)
+    if S.dtype != torch.float32:
+        S = S.to(torch.float32)
+    r_idx, _, part = ops.topk_lists(S, k)
+    c_idx, _ = ops.topk_merge_cols([part], k)
+    i_rank, _, t_rank, _, _ = ops.rank_counts(S, im_div)
+    fine_i = score_fn(r_idx, 'image')
+    fine_t = score_fn(c_idx, 'caption')
+    ri, rv, _ = ops.rerank_lists(r_idx, fine_i)
+    ci, cv, _ = ops.rerank_lists(c_idx, fine_t)
+    lists = {'i2t_topk': ri.cpu().numpy().astype(np.int64), 'i2t_topk_scores': rv.cpu().numpy(),
+             't2i_topk': ci.cpu().numpy().astype(np.int64), 't2i_topk_scores': cv.cpu().numpy()}
+    i_ranks = rerank_rank_vector(lists['i2t_topk'], i_rank.cpu().numpy(), 'i2t', im_div)
+    t_ranks = rerank_rank_vector(lists['t2i_topk'], t_rank.cpu().numpy(), 't2i', im_div)
+    return ops.recall_from_ranks(i_ranks), ops.recall_from_ranks(t_ranks), (i_ranks, t_ranks), lists
+
+
+def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
+    """score_fn of `rerank` for a SCAN model: its word-level caption embeddings packed once, the pair workspace prepared once."""
+    cfg = model.config
+    dev = torch.device('cuda', torch.cuda.current_device())
+    lens = np.asarray(cap_lens, dtype=np.int64)
+    images = torch.from_numpy(np.ascontiguousarray(img_embs)).to(dev)
+    caps = torch.from_numpy(np.ascontiguousarray(cap_embs)).to(dev)
+    L = caps.shape[1]
+    keep = (torch.arange(L, device=dev)[None, :] < torch.from_numpy(lens).to(dev)[:, None]).reshape(-1)
+    words = caps.reshape(-1, caps.shape[2])[keep].contiguous()
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    plan = ops.ScanPlan(off, lens.astype(np.int32), words.shape[0], dev)
+    kw = dict(cross_attn=cfg['cross_attn'], raw_feature_norm=cfg['raw_feature_norm'], agg_func=cfg['agg_func'],
+              lambda_lse=cfg['lambda_lse'], lambda_softmax=cfg['lambda_softmax'])
+    ws = ops.scan_pairs_prepare(images, words, plan, cfg['cross_attn'])
+    return lambda cand, by: ops.scan_candidate_scores(images, words, plan, cand, by, workspace=ws, **kw)
+
+
+def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split='dev', fold5=False):
+    """Coarse-to-fine evaluation: the coarse model (any family evalrank_single scores) shortlists k candidates per query in both
+    directions, the fine model -- SCAN, either cross_attn -- scores only those pairs, Recall@K is that of the reranked ranking
+    (`rerank`).  Writes `<data_name>[_5fold]_rerank<k>_result.yaml` (the coarse-only numbers under 'coarse', the reranked ones
+    under 'rerank') and the reranked lists `<data_name>[_5fold]_rerank<k>.npz` next to the coarse checkpoint."""
+    import os
+    import yaml
+    from ..datamodule import data_loader as data
+    if int(k) < 10:
+        raise ValueError("evalrank_rerank: k = %d < 10: R@10 would not be defined by the shortlist" % int(k))
+    coarse, c_cfg = _load_for_eval(model_path_coarse, data_path)
+    fine, f_cfg = _load_for_eval(model_path_fine, data_path)
+    if f_cfg['name'] != 'SCAN':
+        raise NotImplementedError("evalrank_rerank: the fine model must be SCAN (candidate-list scoring exists for SCAN only), got %s"
+                                  % f_cfg['name'])
+    if f_cfg['data_name'] != c_cfg['data_name']:
+        raise ValueError("evalrank_rerank: the checkpoints name different datasets (%s, %s): their lists would not index the same items"
+                         % (c_cfg['data_name'], f_cfg['data_name']))
+    embs = []
+    for model, cfg in ((coarse, c_cfg), (fine, f_cfg)):
+        loader, _ = data.get_test_loader(split, cfg['data_name'], cfg['batch_size'], cfg['workers'], cfg)
+        embs.append(encode_data(model, loader, islength=cfg['name'] in ['SGRAF', 'SCAN']))
+    (c_img, c_cap, c_len), (f_img, f_cap, f_len) = embs
+    if len(c_img) != len(f_img) or len(c_cap) != len(f_cap):
+        raise ValueError("evalrank_rerank: the two models' loaders hold different item counts (%d / %d images, %d / %d captions)"
+                         % (len(c_img), len(f_img), len(c_cap), len(f_cap)))
+    lists = {}
+
+    def block(sl_img, sl_cap, prefix):
+        sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
+        res_c = cal_recall(sims)
+        fn = _scan_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
+        r, ri, (i_ranks, t_ranks), tl = rerank(sims.astype(np.float32), fn, k)
+        lists.update({prefix + key: v for key, v in tl.items()})
+        res_r = _recall_dict((i_ranks, tl['i2t_topk'][:, 0], t_ranks, tl['t2i_topk'][:, 0]))
+        print("Reranked (k = %d) image to text: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((k,) + tuple(r)))
+        print("Reranked (k = %d) text to image: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((k,) + tuple(ri)))
+        return res_c, res_r
+
+    n = len(c_img)
+    if not fold5:
+        res_c, res_r = block(slice(0, n, 5), slice(None), '')
+        res_dic = {'coarse': res_c, 'rerank': res_r}
+    else:
+        res_dic = {'coarse': {'sum_result': []}, 'rerank': {'sum_result': []}}
+        for i in range(5):
+            res_c, res_r = block(slice(i * 5000, (i + 1) * 5000, 5), slice(i * 5000, (i + 1) * 5000), f'PART_{i + 1}_')
+            for key, part in (('coarse', res_c), ('rerank', res_r)):
+                res_dic[key][f'PART_{i + 1}'] = part
+                res_dic[key]['sum_result'] += part['result']
+        for key in ('coarse', 'rerank'):
+            res_dic[key]['Mean_metrics'] = _mean_metrics(res_dic[key])
+    res_dic['data_name'] = c_cfg['data_name'] + ('_5fold' if fold5 else '')
+    res_dic['k'] = int(k)
+    res_dic['modal_path_coarse'], res_dic['modal_path_fine'] = model_path_coarse, model_path_fine
+    save_dir = os.path.dirname(model_path_coarse)
+    with open(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_result.yaml'), 'w') as f:
+        yaml.safe_dump(_plain(res_dic), f)
+    np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}.npz'), **lists)
+    return res_dic

@@ -1110,3 +1110,169 @@ def topk_merge_cols(parts, k):
     col_val = torch.empty(Nc, int(k), device=keys.device, dtype=torch.float32)
     _lib.check(lib.itr_topk_merge(_p(keys), _p(vals), P, Nc, k_in, int(k), _p(col_idx), _p(col_val), _stream()))
     return col_idx, col_val
+
+
+# ------------------------------------------------------------------------------------------ candidate lists (coarse-to-fine retrieval)
+def _pairs_state(plan, dev):
+    """Device copies of ALL captions' offsets and lengths for the pair kernel (a ScanPlan keeps only those of the captions its
+    column tiles hold); captions of more than SCAN_NT words get length 0 = "not scored by the kernel".  Cached on the plan."""
+    st = getattr(plan, "_pairs_state", None)
+    if st is None or st[0] != dev:
+        klen = np.where(plan.len_host > SCAN_NT, 0, plan.len_host).astype(np.int32)
+        st = (dev, h2d(np.asarray(plan.off_host, dtype=np.int64), dev), h2d(klen, dev))
+        plan._pairs_state = st
+    return st[1], st[2]
+
+
+class ScanPairsWorkspace:
+    """What `scan_pairs_prepare` computed and for what: the buffer, the cross-attention direction, and the identity of the
+    operands (shapes, device pointers, the plan).  `scan_candidate_scores` refuses a workspace prepared for anything else -- its
+    byte size alone would not tell a t2i workspace from an i2t one."""
+
+    def __init__(self, buf, cross_attn, images, words, plan):
+        self.buf, self.cross_attn, self.plan = buf, cross_attn, plan
+        self.key = self._key(images, words)
+
+    @staticmethod
+    def _key(images, words):
+        return (tuple(images.shape), tuple(words.shape), images.data_ptr(), words.data_ptr(), images._version, words._version)
+
+    def check(self, cross_attn, images, words, plan):
+        if self.cross_attn != cross_attn:
+            raise ValueError("scan_candidate_scores: workspace was prepared for cross_attn=%r, called with %r" % (self.cross_attn, cross_attn))
+        if self.plan is not plan or self.key != self._key(images, words):
+            raise ValueError("scan_candidate_scores: workspace was prepared for other images, words or plan (or they were modified since)")
+
+
+def scan_pairs_prepare(images, words, plan, cross_attn='t2i'):
+    """Per image set / caption set precompute of `scan_candidate_scores` (region Gram matrices and word norms for t2i; region
+    norms and caption Gram matrices for i2t): once per image and caption, never per pair.  -> ScanPairsWorkspace, valid for these
+    images, words, plan and cross_attn only."""
+    lib = _lib.load()
+    if cross_attn not in ('t2i', 'i2t'):
+        raise ValueError("unknown cross_attn: %r" % (cross_attn,))
+    images = _dev(images, name="images")
+    words = _dev(words, name="words")
+    Ni, R, D = images.shape
+    if R != SCAN_R:
+        raise NotImplementedError("scan_pairs_prepare: %d regions per image (the pair kernel is built for %d)" % (R, SCAN_R))
+    mode = 0 if cross_attn == 't2i' else 1
+    off, klen = _pairs_state(plan, images.device)
+    wsb = lib.itr_scan_pairs_workspace_bytes(Ni, R, words.shape[0], plan.Nc, mode)
+    ws = torch.empty(max(wsb, 1), device=images.device, dtype=torch.uint8)
+    _lib.check(lib.itr_scan_pairs_prepare(_p(images), _p(words), _p(off), _p(klen), Ni, plan.Nc, words.shape[0], R, D, mode, _p(ws), wsb,
+                                          _stream()))
+    return ScanPairsWorkspace(ws, cross_attn, images, words, plan)
+
+
+def scan_candidate_scores(images, words, plan, cand, by, cross_attn='t2i', raw_feature_norm='clipped_l2norm', agg_func='LogSumExp',
+                          lambda_lse=6.0, lambda_softmax=9.0, workspace=None):
+    """SCAN scores (xattn_score_t2i / _i2t, Objectives.py:329-417) of candidate lists only -- the fine stage of coarse-to-fine
+    retrieval.  With S the matrix `scan_xattn_scores` would return:
+      by='caption': cand int32 [Nc, K] image indices   -> [Nc, K], out[c, k] = S[cand[c, k], c]
+      by='image':   cand int32 [Ni, K] caption indices -> [Ni, K], out[i, k] = S[i, cand[i, k]]
+    Only the listed pairs are computed (csrc/scan_pairs.hip), each to the same bits whatever else is listed.  Duplicates inside
+    a list are allowed; any K >= 1; an empty dimension gives an empty result.  Captions of 65..96 words are scored by the pair
+    path of the training kernels on their listed images (correct, not fast).  `workspace`: scan_pairs_prepare's, to reuse it."""
+    lib = _lib.load()
+    if cross_attn not in ('t2i', 'i2t'):
+        raise ValueError("unknown first norm type:", raw_feature_norm)
+    if raw_feature_norm not in _NORMS:
+        raise ValueError("unknown first norm type:", raw_feature_norm)
+    if agg_func not in _AGGS:
+        raise ValueError("unknown aggfunc: {}".format(agg_func))
+    if by not in ('caption', 'image'):
+        raise ValueError("scan_candidate_scores: by must be 'caption' or 'image', got %r" % (by,))
+    images = _dev(images, name="images")
+    words = _dev(words, name="words")
+    cand = _dev(cand, torch.int32, name="cand")
+    if cand.dim() != 2:
+        raise ValueError("scan_candidate_scores: cand must be 2-D, got shape %s" % (tuple(cand.shape),))
+    Ni, R, D = images.shape
+    Nc = plan.Nc
+    dev = images.device
+    n_q, n_t = (Nc, Ni) if by == 'caption' else (Ni, Nc)          # queries (lists), targets (what a list indexes)
+    if cand.shape[0] != n_q:
+        raise ValueError("scan_candidate_scores: by=%r needs %d lists, got %d" % (by, n_q, cand.shape[0]))
+    K = cand.shape[1]
+    out = torch.empty(n_q, K, device=dev, dtype=torch.float32)
+    if n_q == 0 or K == 0:
+        return out
+    if R != SCAN_R:
+        raise NotImplementedError("scan_candidate_scores: %d regions per image (the pair kernel is built for %d)" % (R, SCAN_R))
+    if len(plan.len_host) and int(plan.len_host.max()) > SCAN_PAIR_MAXW:
+        raise NotImplementedError("scan_candidate_scores: captions of %d words (supported: <= %d)" % (int(plan.len_host.max()), SCAN_PAIR_MAXW))
+    lo, hi = torch.aminmax(cand)                                  # one device reduction: nothing out of range reaches the kernel
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi >= n_t:
+        raise ValueError("scan_candidate_scores: candidate index out of range [0, %d): min %d, max %d" % (n_t, lo, hi))
+    if n_q * K >= 2 ** 31:
+        raise NotImplementedError("scan_candidate_scores: %d pairs; split the lists" % (n_q * K))
+    # ---- caption-major (CSR) form, on the device: no dense intermediate
+    flat = cand.reshape(-1).to(torch.int64)
+    qid = torch.arange(n_q, device=dev, dtype=torch.int64).repeat_interleave(K)
+    caps, imgs = (qid, flat) if by == 'caption' else (flat, qid)
+    slot = torch.arange(n_q * K, device=dev, dtype=torch.int64)
+    if plan.long_idx is not None:
+        is_long = torch.zeros(Nc, device=dev, dtype=torch.bool)
+        is_long[h2d(plan.long_idx, dev)] = True
+        lm = is_long[caps]
+        _scan_long_caption_pairs(images, words, plan, caps[lm], imgs[lm], slot[lm], out, cross_attn, raw_feature_norm, agg_func,
+                                 lambda_lse, lambda_softmax)
+        caps, imgs, slot = caps[~lm], imgs[~lm], slot[~lm]
+    if by == 'image' and caps.numel():
+        caps, order = torch.sort(caps, stable=True)
+        imgs, slot = imgs[order], slot[order]
+    P = caps.numel()
+    if P == 0:
+        return out
+    cap_ptr = torch.zeros(Nc + 1, device=dev, dtype=torch.int32)
+    cap_ptr[1:] = torch.cumsum(torch.bincount(caps, minlength=Nc), 0).to(torch.int32)
+    pair_img, pair_out = imgs.to(torch.int32), slot.to(torch.int32)
+    mode = 0 if cross_attn == 't2i' else 1
+    off, klen = _pairs_state(plan, dev)
+    if workspace is not None:
+        if not isinstance(workspace, ScanPairsWorkspace):
+            raise TypeError("scan_candidate_scores: workspace must come from scan_pairs_prepare")
+        workspace.check(cross_attn, images, words, plan)
+    ws = (workspace if workspace is not None else scan_pairs_prepare(images, words, plan, cross_attn)).buf
+    _lib.check(lib.itr_scan_pair_scores(
+        _p(images), _p(words), _p(off), _p(klen), _p(cap_ptr), _p(pair_img), _p(pair_out), P, Ni, Nc, words.shape[0], R, D, mode,
+        _NORMS[raw_feature_norm], _AGGS[agg_func], float(lambda_softmax), float(lambda_lse), _p(out), out.numel(), _p(ws), ws.numel(),
+        _stream()))
+    return out
+
+
+def _scan_long_caption_pairs(images, words, plan, caps, imgs, slot, out, cross_attn, norm, agg, lambda_lse, lambda_softmax):
+    """Listed pairs of captions with 65..96 words: the one-workgroup-per-pair forward of the training path on each such caption's
+    listed images, then a gather into the lists' slots."""
+    from . import autograd
+    if caps.numel() == 0:
+        return
+    fn = autograd.scan_t2i_scores if cross_attn == 't2i' else autograd.scan_i2t_scores
+    flat = out.view(-1)
+    with torch.no_grad():
+        for c in torch.unique(caps).tolist():
+            m = caps == c
+            sel, inv = torch.unique(imgs[m], return_inverse=True)
+            o, l = int(plan.off_host[c]), int(plan.len_host[c])
+            col = fn(images[sel].contiguous(), words[o:o + l].contiguous(), np.zeros(1, np.int64), np.asarray([l], np.int32), norm, agg,
+                     lambda_lse, lambda_softmax)
+            flat[slot[m]] = col.reshape(-1)[inv]
+
+
+def rerank_lists(idx, val):
+    """Re-order K-lists by new scores: idx int32 [n, K] candidates (in coarse order), val float32 [n, K] their new scores
+    -> (idx_sorted, val_sorted, perm) in the ranker's order (larger score first, the higher index on exact ties, -0.0 == +0.0,
+    NaN as +inf; equal entries keep their coarse order); perm[n, K] = old position of each entry.  1 <= K <= TOPK_MAX."""
+    lib = _lib.load()
+    idx = _dev(idx, torch.int32, name="idx")
+    val = _dev(val, torch.float32, name="val")
+    if idx.dim() != 2 or idx.shape != val.shape:
+        raise ValueError("rerank_lists: idx and val must be 2-D of one shape, got %s and %s" % (tuple(idx.shape), tuple(val.shape)))
+    n, K = idx.shape
+    io, vo, po = torch.empty_like(idx), torch.empty_like(val), torch.empty_like(idx)
+    if n == 0:
+        return io, vo, po
+    _lib.check(lib.itr_rerank_lists(_p(idx), _p(val), n, K, _p(io), _p(vo), _p(po), _stream()))
+    return io, vo, po

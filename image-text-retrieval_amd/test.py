@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Evaluate checkpoints like the reference's test.py:  python test.py MODEL_PATH [MODEL_PATH_2] [--data-path P]
-[--split test|testall|dev] [--fold5] [--topk K]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
-(and with --topk K the top-K retrieval lists of every query in <data_name>[_5fold]_{single,ensemble}_top<K>.npz)"""
+[--split test|testall|dev] [--fold5] [--topk K] [--rerank K]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
+(and with --topk K the top-K retrieval lists of every query in <data_name>[_5fold]_{single,ensemble}_top<K>.npz).
+python test.py COARSE_PATH FINE_PATH --rerank K: coarse-to-fine retrieval, the first model shortlists K candidates per query and the
+second (SCAN) scores only those  ->  <data_name>[_5fold]_rerank<K>_result.yaml and <data_name>[_5fold]_rerank<K>.npz"""
 import argparse
 import os
 import sys
@@ -19,8 +21,16 @@ if __name__ == "__main__":
                     help="sharded device-resident evaluation (evalpipe.evaluate_precomp); run under torch.distributed.run for >1 GPU")
     ap.add_argument("--topk", type=int, default=0, metavar="K",
                     help="also write the top-K retrieved items of every query (indices and scores) to <data_name>..._top<K>.npz")
+    ap.add_argument("--rerank", type=int, default=0, metavar="K",
+                    help="two checkpoints COARSE FINE: FINE (SCAN) re-scores only COARSE's top-K candidates of every query")
     a = ap.parse_args()
-    if a.fast:
+    if a.rerank:
+        if len(a.model_path) != 2:
+            ap.error("--rerank needs two checkpoints: COARSE FINE")
+        if a.fast or a.topk:
+            ap.error("--rerank does not combine with --fast or --topk (the reranked lists are written to ..._rerank<K>.npz)")
+        evaluation.evalrank_rerank(a.model_path[0], a.model_path[1], a.rerank, data_path=a.data_path, split=a.split, fold5=a.fold5)
+    elif a.fast:
         import torch
         import torch.distributed as dist
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))

@@ -36,6 +36,7 @@ typedef void *itr_stream_t;
 
 const char *itr_last_error(void);
 /* ABI version, bumped on any signature change. */
+#define ITR_ABI_VERSION 33
 int itr_abi_version(void);
 
 /* ---- a1: l2norm / l1norm  (itr/modalmodule/utils.py:4-15) ----------------------------
@@ -395,6 +396,35 @@ int itr_topk_merge(const uint64_t *part_key, const float *part_val, int n_parts,
                    int32_t *col_idx, float *col_val, itr_stream_t stream);
 int itr_topk_f64(const double *S, int64_t ldS, int64_t n_rows, int64_t Nc, int K, int32_t *row_idx, double *row_val,
                  int32_t *col_idx, double *col_val, itr_stream_t stream);
+
+/* ---- a6 on candidate lists: xattn_score_t2i / xattn_score_i2t (Objectives.py:329-476) for LISTED (image, caption) pairs ----
+ * The fine stage of coarse-to-fine retrieval: only the P listed pairs are scored (csrc/scan_pairs.hip), with the arithmetic of
+ * itr_scan_xattn_scores (exact fp32 dot products, Gram-form cosine; same mode / norm / agg codes, lambda_softmax, lambda_lse).
+ * The list is caption-major (CSR): the pairs of caption c are p in [cap_ptr[c], cap_ptr[c + 1]), pair p is
+ * (image pair_img[p], caption c) and its score goes to out[pair_out[p]].  Duplicates are allowed.  A pair's score depends on
+ * that pair alone: the same bits whatever else is listed, in whatever order.
+ *   words [n_rows, D]; caption c = rows cap_off[c] .. cap_off[c] + cap_len[c] - 1, cap_len[c] in 1..64, or 0 for a caption
+ *   that is not scored here (it must have no pairs).  R = 36 and D % 16 == 0, else ITR_ERR_UNSUPPORTED.
+ *   An image index outside [0, Ni) is never dereferenced: that pair's score is NaN; an output slot outside [0, out_len) is skipped.
+ * itr_scan_pairs_prepare fills the workspace (itr_scan_pairs_workspace_bytes) ONCE per image set and caption set: mode 0 the
+ * regions' Gram matrices and the word norms, mode 1 the region norms and the captions' Gram matrices; itr_scan_pair_scores
+ * may then be called for any number of lists with the same workspace, mode and operands. */
+size_t itr_scan_pairs_workspace_bytes(int64_t Ni, int R, int64_t n_rows, int64_t Nc, int mode);
+int itr_scan_pairs_prepare(const float *img, const float *words, const int64_t *cap_off, const int32_t *cap_len, int64_t Ni,
+                           int64_t Nc, int64_t n_rows, int R, int D, int mode, void *workspace, size_t workspace_bytes,
+                           itr_stream_t stream);
+int itr_scan_pair_scores(const float *img, const float *words, const int64_t *cap_off, const int32_t *cap_len,
+                         const int32_t *cap_ptr, const int32_t *pair_img, const int32_t *pair_out, int64_t P, int64_t Ni,
+                         int64_t Nc, int64_t n_rows, int R, int D, int mode, int norm, int agg, float lambda_softmax,
+                         float lambda_lse, float *out, int64_t out_len, void *workspace, size_t workspace_bytes,
+                         itr_stream_t stream);
+/* Re-order n lists of K candidates by new scores (evaluation.py:169, :209: the order np.argsort(...)[::-1] gives these K
+ * candidates): idx [n, K] candidates, val [n, K] their new scores -> idx_out / val_out in the ranker's order (larger score
+ * first, the higher index on exact ties, -0.0 == +0.0, NaN as +inf; of two entries with the same candidate and score the one
+ * that stood first stays first), scores with their original bits, perm_out [n, K] = old position of each entry.
+ * 1 <= K <= ITR_TOPK_MAX; outputs must not alias inputs. */
+int itr_rerank_lists(const int32_t *idx, const float *val, int64_t n, int K, int32_t *idx_out, float *val_out,
+                     int32_t *perm_out, itr_stream_t stream);
 
 /* ---- a14: the training step  model.train_emb (itr/modalmodule/Models.py:198-225, :115-145): forward -> loss ->
  * backward -> clip_grad_norm_(2.0) -> Adam.  Backward contractions are itr_gemm_nt on transposed operands;
