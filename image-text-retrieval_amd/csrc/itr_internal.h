@@ -82,11 +82,37 @@ __global__ void sq_prefix_kernel(const int32_t *__restrict__ len, int64_t n, int
 size_t sgr_fused_workspace_bytes(int64_t n_groups, int64_t n_caps, int sgr_step);
 int sgr_fused_prepare(const int32_t *grp_begin, const int32_t *grp_order, int64_t n_groups, int64_t n_caps, const int32_t *cap_len,
                       const int32_t *cap_col, const float *const *wq, const float *const *wg, int sgr_step, void *ws, int *bad_flag, hipStream_t st);
+int sgr_fused_plan_groups(const int32_t *grp_begin, const int32_t *grp_order, int64_t n_groups, int64_t n_caps, const int32_t *cap_len,
+                          const int32_t *cap_col, int sgr_step, void *ws, int *bad_flag, hipStream_t st);
+size_t sgr_fused_weights_bytes(int sgr_step);
+int sgr_fused_pack_weights(const float *const *wq, const float *const *wg, int sgr_step, void *wbuf, hipStream_t st);
+// packed_weights: null = the copy sgr_fused_prepare put into `ws`; else sgr_fused_pack_weights' buffer
 int sgr_fused_scores(const float *xloc, const float *xglo, void *ws, int64_t n_groups, int64_t n_caps, int64_t nb, int64_t Nc, int64_t ncols,
-                     const float *const *vq, const float *const *bg, int sgr_step, float *y0, bool persistent_walk, hipStream_t st);
+                     const float *const *vq, const float *const *bg, int sgr_step, float *y0, bool persistent_walk, hipStream_t st,
+                     const void *packed_weights = nullptr);
 int sgr_fused_finish(void *ws, int64_t n_groups, int64_t n_caps, int sgr_step, int64_t Ni, float *S, int64_t ldS, hipStream_t st);
+// ---- sgraf.hip: pieces of itr_sgraf_scores that the candidate-list entry (sgraf_pairs.hip) runs as well
+int sgraf_global_nodes(const float *img, const float *words, const int64_t *cap_off, const int32_t *cap_len, int64_t Ni, int64_t Nc, int64_t n_rows,
+                       int D, const itr_sgraf_weights *w, float *img_ave, float *g_emb_v, float *l_emb_v, float *img_glo, float *l_emb_t,
+                       float *cap_ave, float *g_emb_t, float *cap_glo, const char *who, itr_stream_t stream);
+int sgraf_fold_weights(const itr_sgraf_weights *w, int S, int sgr_step, float *WqT, float *WkT, float *const *Wfold, float *const *vfold, hipStream_t st);
+struct SgrafStage {
+    float *Xglo, *Xloc, *Qloc, *Qglo, *Yloc, *Yglo;     // node rows [nb * ldg, S] / [nb * ncols, S]; Q*, Yloc: step-by-step chain only
+    const int32_t *cap_col, *cap_len;                   // per caption: first column of its words in a row of Xloc, word count
+    int64_t Nc, ncols, ldg;
+    int S, module, sgr_step, max_len;
+    bool fused, persistent;
+    const itr_sgraf_weights *w;
+    float *const *Wfold, *const *vfold;
+    void *fused_ws;
+    int64_t n_node_groups;
+    const void *packed_weights;                         // sgr_fused_scores' packed_weights
+};
+int sgraf_pair_stage(const SgrafStage &s, int64_t nb, float *Sout, int64_t ldS, int64_t i0, hipStream_t st);
 // ---- sgraf_loc.hip
 int sgraf_loc_fused(const float *P, const float *cn, const float *img, const float *wtiled, const float *W, const float *bias, float *X,
                     int64_t nb, int64_t n_tiles, int D, hipStream_t st);
+int sgraf_loc_items(const float *P, const float *cn, const float *img, int64_t Ni, const int32_t *tile_img, const float *wtiled, const float *W,
+                    const float *bias, float *X, int64_t n_tiles, int D, hipStream_t st);
 
 }  // namespace itr

@@ -919,16 +919,16 @@ static SgrWs sgr_carve(void *ws, int64_t n_groups, int64_t n_caps, int sgr_step)
     w.gcount = c.take<int32_t>(256);
     w.cap_bad = c.take<int32_t>((size_t)n_caps * 4);
     w.frag = c.take<float4>((size_t)sgr_step * 2 * SF_S * SF_S * 4);
-    w.wT = c.take<float>((size_t)SF_S * SF_S * 4);
+    w.wT = sgr_step > 0 ? c.take<float>((size_t)SF_S * SF_S * 4) : nullptr;      // (sgr_step 0: no weight copies, sgr_fused_scores gets packed_weights)
     c.take(256);
     w.bytes = c.bytes;
     return w;
 }
 size_t sgr_fused_workspace_bytes(int64_t n_groups, int64_t n_caps, int sgr_step) { return sgr_carve(nullptr, n_groups, n_caps, sgr_step).bytes; }
 
-// One-time preparation per itr_sgraf_scores call: group records, the two class lists, fragment-ordered weights.
-int sgr_fused_prepare(const int32_t *grp_begin, const int32_t *grp_order, int64_t n_groups, int64_t n_caps, const int32_t *cap_len,
-                      const int32_t *cap_col, const float *const *wq, const float *const *wg, int sgr_step, void *ws, int *bad_flag, hipStream_t st) {
+// The group records and the two class lists of a caption set (per itr_sgraf_scores call; per chunk of listed pairs in sgraf_pairs.hip).
+int sgr_fused_plan_groups(const int32_t *grp_begin, const int32_t *grp_order, int64_t n_groups, int64_t n_caps, const int32_t *cap_len,
+                          const int32_t *cap_col, int sgr_step, void *ws, int *bad_flag, hipStream_t st) {
     const SgrWs w = sgr_carve(ws, n_groups, n_caps, sgr_step);
     ITR_CHECK_HIP(hipMemsetAsync(w.cap_bad, 0, (size_t)n_caps * 4, st));
     hipLaunchKernelGGL(sgr_group_meta_kernel, dim3((unsigned)ceil_div(n_groups, 256)), dim3(256), 0, st, grp_begin, grp_order, cap_len, cap_col,
@@ -936,14 +936,34 @@ int sgr_fused_prepare(const int32_t *grp_begin, const int32_t *grp_order, int64_
     ITR_CHECK_LAUNCH("sgr group meta");
     hipLaunchKernelGGL(sgr_group_classify_kernel, dim3(1), dim3(1024), 0, st, w.cls, n_groups, w.glist, w.gcount);
     ITR_CHECK_LAUNCH("sgr group classes");
+    return ITR_OK;
+}
+
+// Fragment-ordered weights of every step, then the last step's folded query weight transposed: [sgr_step * 2 * 256 * 256 floats][256 * 256]
+size_t sgr_fused_weights_bytes(int sgr_step) { return align256((size_t)sgr_step * 2 * SF_S * SF_S * 4) + align256((size_t)SF_S * SF_S * 4); }
+static int sgr_pack_weights_into(float4 *frag, float *wT, const float *const *wq, const float *const *wg, int sgr_step, hipStream_t st) {
     for (int k = 0; k < sgr_step; ++k) {
-        hipLaunchKernelGGL(sgr_pack_weight_kernel, dim3(64), dim3(256), 0, st, wq[k], w.frag + (size_t)(2 * k) * SF_S * SF_S / 4);
-        hipLaunchKernelGGL(sgr_pack_weight_kernel, dim3(64), dim3(256), 0, st, wg[k], w.frag + (size_t)(2 * k + 1) * SF_S * SF_S / 4);
+        hipLaunchKernelGGL(sgr_pack_weight_kernel, dim3(64), dim3(256), 0, st, wq[k], frag + (size_t)(2 * k) * SF_S * SF_S / 4);
+        hipLaunchKernelGGL(sgr_pack_weight_kernel, dim3(64), dim3(256), 0, st, wg[k], frag + (size_t)(2 * k + 1) * SF_S * SF_S / 4);
     }
     ITR_CHECK_LAUNCH("sgr pack weights");
-    hipLaunchKernelGGL(sgr_transpose_weight_kernel, dim3(SF_S * SF_S / 256), dim3(256), 0, st, wq[sgr_step - 1], w.wT);
+    hipLaunchKernelGGL(sgr_transpose_weight_kernel, dim3(SF_S * SF_S / 256), dim3(256), 0, st, wq[sgr_step - 1], wT);
     ITR_CHECK_LAUNCH("sgr transpose weights");
     return ITR_OK;
+}
+int sgr_fused_pack_weights(const float *const *wq, const float *const *wg, int sgr_step, void *wbuf, hipStream_t st) {
+    float4 *frag = static_cast<float4 *>(wbuf);
+    float *wT = reinterpret_cast<float *>(static_cast<char *>(wbuf) + align256((size_t)sgr_step * 2 * SF_S * SF_S * 4));
+    return sgr_pack_weights_into(frag, wT, wq, wg, sgr_step, st);
+}
+
+// One-time preparation per itr_sgraf_scores call: group records, the two class lists, fragment-ordered weights.
+int sgr_fused_prepare(const int32_t *grp_begin, const int32_t *grp_order, int64_t n_groups, int64_t n_caps, const int32_t *cap_len,
+                      const int32_t *cap_col, const float *const *wq, const float *const *wg, int sgr_step, void *ws, int *bad_flag, hipStream_t st) {
+    const int rc = sgr_fused_plan_groups(grp_begin, grp_order, n_groups, n_caps, cap_len, cap_col, sgr_step, ws, bad_flag, st);
+    if (rc != ITR_OK) return rc;
+    const SgrWs w = sgr_carve(ws, n_groups, n_caps, sgr_step);
+    return sgr_pack_weights_into(w.frag, w.wT, wq, wg, sgr_step, st);
 }
 
 // After the last block of images: NaN into the score columns of the captions whose group was refused (a wrong hand-made plan).
@@ -997,9 +1017,15 @@ static int sgr_fused_launch_class(SgrFusedArgs g, int cls_index, int64_t n_group
 // Runs the graph steps up to the last step's attention; y0 [nb][Nc][256] receives y of node 0 of every graph.  The caller finishes:
 // x_0 = relu(W_g y + b) as one GEMM over nb * Nc rows, then sigmoid(sim_eval_w . x_0 + b) (sgraf.hip).
 int sgr_fused_scores(const float *xloc, const float *xglo, void *ws, int64_t n_groups, int64_t n_caps, int64_t nb, int64_t Nc, int64_t ncols,
-                     const float *const *vq, const float *const *bg, int sgr_step, float *y0, bool persistent_walk, hipStream_t st) {
+                     const float *const *vq, const float *const *bg, int sgr_step, float *y0, bool persistent_walk, hipStream_t st,
+                     const void *packed_weights) {
     if (nb == 0 || n_groups == 0) return ITR_OK;
-    const SgrWs w = sgr_carve(ws, n_groups, n_caps, sgr_step);
+    ITR_REQUIRE(sgr_step >= 1 && sgr_step <= 8, "sgr_fused_scores: sgr_step must be in [1, 8]");      // (a workspace carved with 0 steps has no weight copies: only with packed_weights)
+    SgrWs w = sgr_carve(ws, n_groups, n_caps, packed_weights ? 0 : sgr_step);      // (a workspace without weight copies: sized with sgr_step 0)
+    if (packed_weights) {   // sgr_fused_pack_weights' buffer (packed once for many plans) instead of this workspace's own copy
+        w.frag = static_cast<float4 *>(const_cast<void *>(packed_weights));
+        w.wT = reinterpret_cast<float *>(static_cast<char *>(const_cast<void *>(packed_weights)) + align256((size_t)sgr_step * 2 * SF_S * SF_S * 4));
+    }
     SgrFusedArgs g;
     memset(&g, 0, sizeof(g));
     g.xloc = xloc; g.xglo = xglo;

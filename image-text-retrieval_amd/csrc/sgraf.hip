@@ -388,6 +388,121 @@ __global__ __launch_bounds__(256) void sgr_final_kernel(const float *__restrict_
     if (lane == 0) S[(img_index0 + pair / Nc) * ldS + pair % Nc] = 1.f / (1.f + expf(-s));
 }
 
+// The global nodes' operands, once per call: img_glo [Ni, D] (VisualSA :491-507) and cap_glo [Nc, D] (TextSA :543-559).  The other buffers are
+// scratch: img_ave / g_emb_v [Ni, D], l_emb_v [Ni * 36, D], l_emb_t [n_rows, D], cap_ave / g_emb_t [Nc, D].
+int sgraf_global_nodes(const float *img, const float *words, const int64_t *cap_off, const int32_t *cap_len, int64_t Ni, int64_t Nc, int64_t n_rows,
+                       int D, const itr_sgraf_weights *w, float *img_ave, float *g_emb_v, float *l_emb_v, float *img_glo, float *l_emb_t,
+                       float *cap_ave, float *g_emb_t, float *cap_glo, const char *who, itr_stream_t stream) {
+    hipStream_t st = as_stream(stream);
+    int rc;
+#define SG_TRY(x) { rc = (x); if (rc != ITR_OK) return rc; }
+    // ---- global nodes: VisualSA (:491-507)
+    ITR_REQUIRE(Ni <= 65535, "%s: at most 65535 images per call", who);
+    SG_TRY(itr_mean_mid(img, img_ave, Ni, SC_R, D, stream));
+    SG_TRY(gemm_nt(img, D, w->v_loc_w, D, w->v_loc_b, l_emb_v, D, Ni * SC_R, D, D, 0, st));
+    {
+        dim3 grid((unsigned)ceil_div(D, 256), (unsigned)1);
+        // rows can exceed 65535: launch in slabs
+        for (int64_t r0 = 0; r0 < Ni * SC_R; r0 += 65520) {   // 65520 is a multiple of 36
+            const int64_t nr = (Ni * SC_R - r0 < 65520) ? Ni * SC_R - r0 : 65520;
+            hipLaunchKernelGGL(bn_tanh_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)nr), dim3(256), 0, st,
+                               l_emb_v + r0 * D, nr, D, 1, SC_R, w->v_loc_bn_w, w->v_loc_bn_b, w->v_loc_bn_mean, w->v_loc_bn_var);
+        }
+        ITR_CHECK_LAUNCH("sgraf bn_tanh (local)");
+        (void)grid;
+    }
+    SG_TRY(gemm_nt(img_ave, D, w->v_glo_w, D, w->v_glo_b, g_emb_v, D, Ni, D, D, 0, st));
+    hipLaunchKernelGGL(bn_tanh_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)Ni), dim3(256), 0, st, g_emb_v, Ni, D, 0, 1,
+                       w->v_glo_bn_w, w->v_glo_bn_b, w->v_glo_bn_mean, w->v_glo_bn_var);
+    ITR_CHECK_LAUNCH("sgraf bn_tanh (global)");
+    hipLaunchKernelGGL(sa_pool_kernel, dim3((unsigned)Ni), dim3(256), 0, st, img, l_emb_v, g_emb_v, w->v_com_w, w->v_com_b,
+                       (const int64_t *)nullptr, (const int32_t *)nullptr, SC_R, D, img_glo);
+    ITR_CHECK_LAUNCH("sgraf sa_pool (image)");
+    // ---- TextSA (:543-559)
+    SG_TRY(gemm_nt(words, D, w->t_loc_w, D, w->t_loc_b, l_emb_t, D, n_rows, D, D, 2 /*tanh*/, st));
+    hipLaunchKernelGGL(seg_mean_kernel, dim3((unsigned)Nc), dim3(256), 0, st, words, cap_off, cap_len, D, cap_ave);
+    ITR_CHECK_LAUNCH("sgraf seg_mean");
+    SG_TRY(gemm_nt(cap_ave, D, w->t_glo_w, D, w->t_glo_b, g_emb_t, D, Nc, D, D, 2, st));
+    hipLaunchKernelGGL(sa_pool_kernel, dim3((unsigned)Nc), dim3(256), 0, st, words, l_emb_t, g_emb_t, w->t_com_w, w->t_com_b, cap_off,
+                       cap_len, 0, D, cap_glo);
+    ITR_CHECK_LAUNCH("sgraf sa_pool (caption)");
+#undef SG_TRY
+    return ITR_OK;
+}
+
+// q' = (Wk^T Wq) x + Wk^T bq per step (see itr_sgraf_scores): Wfold[k] [S, S], vfold[k] [S]; WqT / WkT: [S, S] scratch
+int sgraf_fold_weights(const itr_sgraf_weights *w, int S, int sgr_step, float *WqT, float *WkT, float *const *Wfold, float *const *vfold, hipStream_t st) {
+    int rc;
+#define SG_TRY(x) { rc = (x); if (rc != ITR_OK) return rc; }
+    const unsigned tb = (unsigned)ceil_div((int64_t)S * S, 256);
+    for (int k = 0; k < sgr_step; ++k) {
+        hipLaunchKernelGGL(transpose_small_kernel, dim3(tb), dim3(256), 0, st, w->sgr_q_w[k], S, S, WqT);
+        hipLaunchKernelGGL(transpose_small_kernel, dim3(tb), dim3(256), 0, st, w->sgr_k_w[k], S, S, WkT);
+        ITR_CHECK_LAUNCH("sgraf weight transpose");
+        // Wfold[b][a] = sum_o Wk[o][b] Wq[o][a];  vfold[b] = sum_o bq[o] Wk[o][b]
+        SG_TRY(gemm_nt(WkT, S, WqT, S, nullptr, Wfold[k], S, S, S, S, 0, st));
+        SG_TRY(gemm_nt(w->sgr_q_b[k], S, WkT, S, nullptr, vfold[k], S, 1, S, S, 0, st));
+    }
+#undef SG_TRY
+    return ITR_OK;
+}
+
+// The pair stage of one block of nb image rows whose node rows are in place (sim_loc in Xloc, sim_glo in Xglo): SAF, or the SGR steps, and
+// the final score into Sout[(i0 + ii) * ldS + c].  Shared by the dense call and the candidate lists (sgraf_pairs.hip: nb = 1, the "captions"
+// are the listed pairs of a chunk).
+int sgraf_pair_stage(const SgrafStage &s, int64_t nb, float *Sout, int64_t ldS, int64_t i0, hipStream_t st) {
+    int rc;
+#define SG_TRY(x) { rc = (x); if (rc != ITR_OK) return rc; }
+    const itr_sgraf_weights *w = s.w;
+    const int64_t Nc = s.Nc, ncols = s.ncols, ldg = s.ldg;
+    const int S = s.S, module = s.module, sgr_step = s.sgr_step, max_len = s.max_len;
+    PairArgs pa{s.Xglo, s.Xloc, s.cap_col, s.cap_len, Nc, ncols, S, ldg};
+    const int64_t npairs = nb * Nc;
+    if (module == 0) {
+        hipLaunchKernelGGL(saf_pair_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, pa, w->saf_w, w->saf_b, w->saf_bn_w,
+                           w->saf_bn_b, w->saf_bn_mean, w->saf_bn_var, w->eval_w, w->eval_b, npairs, Sout, ldS, i0);
+        ITR_CHECK_LAUNCH("sgraf saf_pair");
+    } else if (s.fused) {
+        // all the graph steps up to the last step's attention in one workgroup per group of captions; the last step's graph
+        // projection of node 0 (the only node read afterwards, Fusionmodule.py:443) for ALL the graphs of the block as one GEMM
+        SG_TRY(sgr_fused_scores(s.Xloc, s.Xglo, s.fused_ws, s.n_node_groups, Nc, nb, ldg, ncols, s.vfold, w->sgr_g_b, sgr_step, s.Yglo,
+                                s.persistent, st, s.packed_weights));
+        SG_TRY(gemm_nt(s.Yglo, S, w->sgr_g_w[sgr_step - 1], S, w->sgr_g_b[sgr_step - 1], s.Xglo, S, nb * ldg, S, S, 1 /*relu*/, st));
+        hipLaunchKernelGGL(sgr_final_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, s.Xglo, Nc, S, w->eval_w, w->eval_b,
+                           npairs, Sout, ldS, i0, ldg);
+        ITR_CHECK_LAUNCH("sgraf sgr_final (fused steps)");
+    } else {
+        const int ntmax = (max_len + 1 + 15) / 16;
+        ITR_UNSUPPORTED(S % 16 != 0, "itr_sgraf_scores: SGR needs sim_dim %% 16 == 0");
+        for (int k = 0; k < sgr_step; ++k) {
+            const int last = (k == sgr_step - 1);
+            if (!last) SG_TRY(gemm_nt(s.Xloc, S, s.Wfold[k], S, s.vfold[k], s.Qloc, S, nb * ncols, S, S, 0, st));   // last: only node 0 queries
+            SG_TRY(gemm_nt(s.Xglo, S, s.Wfold[k], S, s.vfold[k], s.Qglo, S, nb * ldg, S, S, 0, st));
+            const dim3 pgrid((unsigned)ceil_div(npairs, 4));
+            auto plds = [](int nt) { return (size_t)4 * (nt * 16) * (nt * 16 + 4) * 4; };   // 4 waves x P[NT*16][NT*16+4]
+            if (ntmax == 1) {
+                hipLaunchKernelGGL(sgr_pair_kernel<1>, pgrid, dim3(256), plds(1), st, pa, s.Qglo, s.Qloc, s.Xglo, s.Xloc, s.Yglo, s.Yloc, npairs, 1, last);
+            } else {
+                hipLaunchKernelGGL(sgr_pair_kernel<2>, pgrid, dim3(256), plds(2), st, pa, s.Qglo, s.Qloc, s.Xglo, s.Xloc, s.Yglo, s.Yloc, npairs, 1, last);
+                if (ntmax > 2) {
+                    ITR_CHECK_LAUNCH("sgraf sgr_pair");
+                    hipLaunchKernelGGL(sgr_pair_kernel<4>, pgrid, dim3(256), plds(4), st, pa, s.Qglo, s.Qloc, s.Xglo, s.Xloc, s.Yglo, s.Yloc, npairs, 3, last);
+                }
+            }
+            ITR_CHECK_LAUNCH("sgraf sgr_pair");
+            // NOTE: a word node is shared by all captions... it is NOT: node rows are per (image, word) and a word
+            // belongs to one caption, so writing Yloc rows per pair is race-free.
+            if (!last) SG_TRY(gemm_nt(s.Yloc, S, w->sgr_g_w[k], S, w->sgr_g_b[k], s.Xloc, S, nb * ncols, S, S, 1 /*relu*/, st));
+            SG_TRY(gemm_nt(s.Yglo, S, w->sgr_g_w[k], S, w->sgr_g_b[k], s.Xglo, S, nb * ldg, S, S, 1, st));
+        }
+        hipLaunchKernelGGL(sgr_final_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, s.Xglo, Nc, S, w->eval_w, w->eval_b,
+                           npairs, Sout, ldS, i0, ldg);
+        ITR_CHECK_LAUNCH("sgraf sgr_final");
+    }
+#undef SG_TRY
+    return ITR_OK;
+}
+
 // Images per block of the pair stage (a multiple of the SCAN image tile).  64 by default since round 4 (rounds 1-3: 16) -- a quarter of
 // the launches, and the persistent SGR kernel's tail (the last, partial round of items over the CUs) is a quarter as large: SGR 1k x 5k
 // 735.8 -> 723.5 ms, SAF 373.3 -> 371.3 (same box; 32: 732.9 / 372.7).  The workspace grows with it (5k x 25k at 64: SAF 38 GB, SGR
@@ -518,36 +633,9 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
     int rc;
 #define SG_TRY(x) { rc = (x); if (rc != ITR_OK) return rc; }
 
-    // ---- global nodes: VisualSA (:491-507)
-    ITR_REQUIRE(Ni <= 65535, "itr_sgraf_scores: at most 65535 images per call");
-    SG_TRY(itr_mean_mid(img, ws.img_ave, Ni, SC_R, D, stream));
-    SG_TRY(gemm_nt(img, D, w->v_loc_w, D, w->v_loc_b, ws.l_emb_v, D, Ni * SC_R, D, D, 0, st));
-    {
-        dim3 grid((unsigned)ceil_div(D, 256), (unsigned)1);
-        // rows can exceed 65535: launch in slabs
-        for (int64_t r0 = 0; r0 < Ni * SC_R; r0 += 65520) {   // 65520 is a multiple of 36
-            const int64_t nr = (Ni * SC_R - r0 < 65520) ? Ni * SC_R - r0 : 65520;
-            hipLaunchKernelGGL(bn_tanh_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)nr), dim3(256), 0, st,
-                               ws.l_emb_v + r0 * D, nr, D, 1, SC_R, w->v_loc_bn_w, w->v_loc_bn_b, w->v_loc_bn_mean, w->v_loc_bn_var);
-        }
-        ITR_CHECK_LAUNCH("sgraf bn_tanh (local)");
-        (void)grid;
-    }
-    SG_TRY(gemm_nt(ws.img_ave, D, w->v_glo_w, D, w->v_glo_b, ws.g_emb_v, D, Ni, D, D, 0, st));
-    hipLaunchKernelGGL(bn_tanh_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)Ni), dim3(256), 0, st, ws.g_emb_v, Ni, D, 0, 1,
-                       w->v_glo_bn_w, w->v_glo_bn_b, w->v_glo_bn_mean, w->v_glo_bn_var);
-    ITR_CHECK_LAUNCH("sgraf bn_tanh (global)");
-    hipLaunchKernelGGL(sa_pool_kernel, dim3((unsigned)Ni), dim3(256), 0, st, img, ws.l_emb_v, ws.g_emb_v, w->v_com_w, w->v_com_b,
-                       (const int64_t *)nullptr, (const int32_t *)nullptr, SC_R, D, ws.img_glo);
-    ITR_CHECK_LAUNCH("sgraf sa_pool (image)");
-    // ---- TextSA (:543-559)
-    SG_TRY(gemm_nt(words, D, w->t_loc_w, D, w->t_loc_b, ws.l_emb_t, D, n_rows, D, D, 2 /*tanh*/, st));
-    hipLaunchKernelGGL(seg_mean_kernel, dim3((unsigned)Nc), dim3(256), 0, st, words, cap_off, cap_len, D, ws.cap_ave);
-    ITR_CHECK_LAUNCH("sgraf seg_mean");
-    SG_TRY(gemm_nt(ws.cap_ave, D, w->t_glo_w, D, w->t_glo_b, ws.g_emb_t, D, Nc, D, D, 2, st));
-    hipLaunchKernelGGL(sa_pool_kernel, dim3((unsigned)Nc), dim3(256), 0, st, words, ws.l_emb_t, ws.g_emb_t, w->t_com_w, w->t_com_b, cap_off,
-                       cap_len, 0, D, ws.cap_glo);
-    ITR_CHECK_LAUNCH("sgraf sa_pool (caption)");
+    // ---- global nodes: VisualSA (:491-507), TextSA (:543-559)
+    SG_TRY(sgraf_global_nodes(img, words, cap_off, cap_len, Ni, Nc, n_rows, D, w, ws.img_ave, ws.g_emb_v, ws.l_emb_v, ws.img_glo, ws.l_emb_t, ws.cap_ave,
+                              ws.g_emb_t, ws.cap_glo, "itr_sgraf_scores", stream));
     // ---- operand prep for the pair stage
     hipLaunchKernelGGL(transpose_img_kernel, dim3((unsigned)ceil_div(D, 64), (unsigned)Ni), dim3(256), 0, st, img, SC_R, D, ws.imgT);
     ITR_CHECK_LAUNCH("sgraf transpose");
@@ -560,17 +648,7 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
     // second term does not depend on j, so it cancels in the softmax:  edge = softmax_j(q'_i . x_j) with
     //     q' = (Wk^T Wq) x + Wk^T bq.
     // One S x S projection per node and step instead of two; the pair kernel reads the nodes themselves as keys.
-    if (module == 1) {
-        const unsigned tb = (unsigned)ceil_div((int64_t)S * S, 256);
-        for (int k = 0; k < sgr_step; ++k) {
-            hipLaunchKernelGGL(transpose_small_kernel, dim3(tb), dim3(256), 0, st, w->sgr_q_w[k], S, S, ws.WqT);
-            hipLaunchKernelGGL(transpose_small_kernel, dim3(tb), dim3(256), 0, st, w->sgr_k_w[k], S, S, ws.WkT);
-            ITR_CHECK_LAUNCH("sgraf weight transpose");
-            // Wfold[b][a] = sum_o Wk[o][b] Wq[o][a];  vfold[b] = sum_o bq[o] Wk[o][b]
-            SG_TRY(gemm_nt(ws.WkT, S, ws.WqT, S, nullptr, ws.Wfold[k], S, S, S, S, 0, st));
-            SG_TRY(gemm_nt(w->sgr_q_b[k], S, ws.WkT, S, nullptr, ws.vfold[k], S, 1, S, S, 0, st));
-        }
-    }
+    if (module == 1) SG_TRY(sgraf_fold_weights(w, S, sgr_step, ws.WqT, ws.WkT, ws.Wfold, ws.vfold, st));
 
     if (module == 1) {
         // rows of captions Nc .. NcP - 1 (and of refused groups) are never written by the pair / fused kernels but run through the GEMMs of
@@ -590,7 +668,11 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
         hipLaunchKernelGGL(glo_onehot_kernel, dim3((unsigned)ceil_div(IB * NcP * SC_R, (int64_t)256)), dim3(256), 0, st, ws.Pg, ws.cng, IB * NcP);
         ITR_CHECK_LAUNCH("sgraf glo one-hot");
     }
-    PairArgs pa{ws.Xglo, ws.Xloc, ws.cap_col, cap_len, Nc, ncols, S, ldg};
+    SgrafStage stg{};
+    stg.Xglo = ws.Xglo, stg.Xloc = ws.Xloc, stg.Qloc = ws.Qloc, stg.Qglo = ws.Qglo, stg.Yloc = ws.Yloc, stg.Yglo = ws.Yglo;
+    stg.cap_col = ws.cap_col, stg.cap_len = cap_len, stg.Nc = Nc, stg.ncols = ncols, stg.ldg = ldg, stg.S = S, stg.module = module;
+    stg.sgr_step = sgr_step, stg.max_len = max_len, stg.fused = fused_sgr, stg.persistent = !(flags & ITR_SGRAF_NON_PERSISTENT), stg.w = w;
+    stg.Wfold = ws.Wfold, stg.vfold = ws.vfold, stg.fused_ws = ws.fused_ws, stg.n_node_groups = n_node_groups;
     for (int64_t i0 = 0; i0 < Ni; i0 += IB) {
         const int64_t nb = (Ni - i0 < IB) ? Ni - i0 : IB;
         // 1. attention weights + context norms  (SCAN_attention: clipped_l2norm, smooth 9)
@@ -618,48 +700,7 @@ extern "C" int itr_sgraf_scores(const float *img, const float *words, const int6
             SG_TRY(gemm_nt(ws.Aglo, D, w->glo_w, D, w->glo_b, ws.Xglo, S, nb * Nc, S, D, 0, st));
             SG_TRY(norm_rows(ws.Xglo, ws.Xglo, nb * Nc, S, 1e-8f, 0, 0, st));
         }
-        const int64_t npairs = nb * Nc;
-        if (module == 0) {
-            hipLaunchKernelGGL(saf_pair_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, pa, w->saf_w, w->saf_b, w->saf_bn_w,
-                               w->saf_bn_b, w->saf_bn_mean, w->saf_bn_var, w->eval_w, w->eval_b, npairs, Sout, ldS, i0);
-            ITR_CHECK_LAUNCH("sgraf saf_pair");
-        } else if (fused_sgr) {
-            // all the graph steps up to the last step's attention in one workgroup per group of captions; the last step's graph
-            // projection of node 0 (the only node read afterwards, Fusionmodule.py:443) for ALL the graphs of the block as one GEMM
-            SG_TRY(sgr_fused_scores(ws.Xloc, ws.Xglo, ws.fused_ws, n_node_groups, Nc, nb, ldg, ncols, ws.vfold, w->sgr_g_b, sgr_step, ws.Yglo,
-                                    !(flags & ITR_SGRAF_NON_PERSISTENT), st));
-            SG_TRY(gemm_nt(ws.Yglo, S, w->sgr_g_w[sgr_step - 1], S, w->sgr_g_b[sgr_step - 1], ws.Xglo, S, nb * ldg, S, S, 1 /*relu*/, st));
-            hipLaunchKernelGGL(sgr_final_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, ws.Xglo, Nc, S, w->eval_w, w->eval_b,
-                               npairs, Sout, ldS, i0, ldg);
-            ITR_CHECK_LAUNCH("sgraf sgr_final (fused steps)");
-        } else {
-            const int ntmax = (max_len + 1 + 15) / 16;
-            ITR_UNSUPPORTED(S % 16 != 0, "itr_sgraf_scores: SGR needs sim_dim %% 16 == 0");
-            for (int k = 0; k < sgr_step; ++k) {
-                const int last = (k == sgr_step - 1);
-                if (!last) SG_TRY(gemm_nt(ws.Xloc, S, ws.Wfold[k], S, ws.vfold[k], ws.Qloc, S, nb * ncols, S, S, 0, st));   // last: only node 0 queries
-                SG_TRY(gemm_nt(ws.Xglo, S, ws.Wfold[k], S, ws.vfold[k], ws.Qglo, S, nb * ldg, S, S, 0, st));
-                const dim3 pgrid((unsigned)ceil_div(npairs, 4));
-                auto plds = [](int nt) { return (size_t)4 * (nt * 16) * (nt * 16 + 4) * 4; };   // 4 waves x P[NT*16][NT*16+4]
-                if (ntmax == 1) {
-                    hipLaunchKernelGGL(sgr_pair_kernel<1>, pgrid, dim3(256), plds(1), st, pa, ws.Qglo, ws.Qloc, ws.Xglo, ws.Xloc, ws.Yglo, ws.Yloc, npairs, 1, last);
-                } else {
-                    hipLaunchKernelGGL(sgr_pair_kernel<2>, pgrid, dim3(256), plds(2), st, pa, ws.Qglo, ws.Qloc, ws.Xglo, ws.Xloc, ws.Yglo, ws.Yloc, npairs, 1, last);
-                    if (ntmax > 2) {
-                        ITR_CHECK_LAUNCH("sgraf sgr_pair");
-                        hipLaunchKernelGGL(sgr_pair_kernel<4>, pgrid, dim3(256), plds(4), st, pa, ws.Qglo, ws.Qloc, ws.Xglo, ws.Xloc, ws.Yglo, ws.Yloc, npairs, 3, last);
-                    }
-                }
-                ITR_CHECK_LAUNCH("sgraf sgr_pair");
-                // NOTE: a word node is shared by all captions... it is NOT: node rows are per (image, word) and a word
-                // belongs to one caption, so writing Yloc rows per pair is race-free.
-                if (!last) SG_TRY(gemm_nt(ws.Yloc, S, w->sgr_g_w[k], S, w->sgr_g_b[k], ws.Xloc, S, nb * ncols, S, S, 1 /*relu*/, st));
-                SG_TRY(gemm_nt(ws.Yglo, S, w->sgr_g_w[k], S, w->sgr_g_b[k], ws.Xglo, S, nb * ldg, S, S, 1, st));
-            }
-            hipLaunchKernelGGL(sgr_final_kernel, dim3((unsigned)ceil_div(npairs, 4)), dim3(256), 0, st, ws.Xglo, Nc, S, w->eval_w, w->eval_b,
-                               npairs, Sout, ldS, i0, ldg);
-            ITR_CHECK_LAUNCH("sgraf sgr_final");
-        }
+        SG_TRY(sgraf_pair_stage(stg, nb, Sout, ldS, i0, st));
     }
     // a refused group of a hand-made node-group plan: NaN in its captions' columns (never uninitialised memory; sgr_fused.hip)
     if (fused_sgr) SG_TRY(sgr_fused_finish(ws.fused_ws, n_node_groups, Nc, sgr_step, Ni, Sout, ldS, st));

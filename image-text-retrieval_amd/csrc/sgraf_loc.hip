@@ -38,6 +38,8 @@ struct LocArgs {
     float *X;              // [nb][ncols][256]  out: l2-normalised local nodes
     int64_t nb, n_tiles;
     int D;
+    const int32_t *tile_img;   // item form (sgraf_loc_items_kernel): image of column tile ct in `img` [Ni][36][D]; nb = 1
+    int64_t Ni;
 };
 
 struct LocSmem {
@@ -45,7 +47,10 @@ struct LocSmem {
     float4 w[2][LPL][LN];   // 64 KB
 };
 
-__global__ __launch_bounds__(256, 2) void sgraf_loc_kernel(LocArgs g) {
+// ITEMS: the image of a column tile comes from g.tile_img (candidate lists, sgraf_pairs.hip: a tile holds listed captions of ONE image)
+// instead of the block's image index; everything else -- the generated D loop, the epilogue -- is the same code.
+template <bool ITEMS>
+__device__ __forceinline__ void sgraf_loc_body(const LocArgs &g) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LocSmem &sm = *reinterpret_cast<LocSmem *>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -74,7 +79,12 @@ __global__ __launch_bounds__(256, 2) void sgraf_loc_kernel(LocArgs g) {
     // Loop-invariant addressing (the fp32 MFMA shares the vector ALU: the compiler's per-load 64-bit address arithmetic was
     // 225 VALU instructions per slice, ~19 % of the matrix time): uniform 64-bit bases advanced by scalar adds + ONE fixed
     // 32-bit per-lane byte offset per operand, loads issued through inline asm with our own s_waitcnt.
-    const char *vbase = reinterpret_cast<const char *>(g.img + ii * SC_R * (int64_t)D);                       // V[k][d]
+    int64_t vimg = ii;
+    if (ITEMS) {
+        const int t = __builtin_amdgcn_readfirstlane(g.tile_img[ct]);
+        vimg = (t >= 0 && t < g.Ni) ? t : 0;                  // (the plan kernel writes valid indices; never read out of bounds)
+    }
+    const char *vbase = reinterpret_cast<const char *>(g.img + vimg * SC_R * (int64_t)D);                     // V[k][d]
     const char *zbase = reinterpret_cast<const char *>(g.wtiled + (ct * SC_NT + 16 * wave) * (int64_t)D);    // E rows of this wave
     const char *wbase = reinterpret_cast<const char *>(g.W);
     const unsigned rowb = (unsigned)D * 4u;
@@ -156,7 +166,8 @@ __global__ __launch_bounds__(256, 2) void sgraf_loc_kernel(LocArgs g) {
             }
     }
 }
-
+__global__ __launch_bounds__(256, 2) void sgraf_loc_kernel(LocArgs g) { sgraf_loc_body<false>(g); }
+__global__ __launch_bounds__(256, 2) void sgraf_loc_items_kernel(LocArgs g) { sgraf_loc_body<true>(g); }
 
 int sgraf_loc_fused(const float *P, const float *cn, const float *img, const float *wtiled, const float *W, const float *bias,
                     float *X, int64_t nb, int64_t n_tiles, int D, hipStream_t st) {
@@ -166,10 +177,24 @@ int sgraf_loc_fused(const float *P, const float *cn, const float *img, const flo
         if (rc != ITR_OK) return rc;
     }
     if (nb == 0 || n_tiles == 0) return ITR_OK;
-    LocArgs g{P, cn, img, wtiled, W, bias, X, nb, n_tiles, D};
+    LocArgs g{P, cn, img, wtiled, W, bias, X, nb, n_tiles, D, nullptr, 0};
     const int64_t grid = ceil_div(n_tiles, (int64_t)8) * 8 * nb;
     hipLaunchKernelGGL(sgraf_loc_kernel, dim3((unsigned)grid), dim3(256), sizeof(LocSmem), st, g);
     ITR_CHECK_LAUNCH("sgraf_loc");
+    return ITR_OK;
+}
+
+// Item form: n_tiles column tiles of one virtual image row; tile t holds words gathered for image tile_img[t] of img [Ni][36][D].
+int sgraf_loc_items(const float *P, const float *cn, const float *img, int64_t Ni, const int32_t *tile_img, const float *wtiled, const float *W,
+                    const float *bias, float *X, int64_t n_tiles, int D, hipStream_t st) {
+    const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(sgraf_loc_items_kernel), sizeof(LocSmem));
+    if (rc != ITR_OK) return rc;
+    if (n_tiles == 0) return ITR_OK;
+    LocArgs g{P, cn, img, wtiled, W, bias, X, 1, n_tiles, D, tile_img, Ni};
+    const int64_t grid = ceil_div(n_tiles, (int64_t)8) * 8;
+    ITR_REQUIRE(grid < (1ll << 31), "sgraf_loc_items: grid too large");
+    hipLaunchKernelGGL(sgraf_loc_items_kernel, dim3((unsigned)grid), dim3(256), sizeof(LocSmem), st, g);
+    ITR_CHECK_LAUNCH("sgraf_loc_items");
     return ITR_OK;
 }
 

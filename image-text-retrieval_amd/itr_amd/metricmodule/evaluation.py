@@ -399,7 +399,7 @@ def evalrank_ensemble(model_path, model_path2, data_path=None, split='dev', fold
 
 # ---------------------------------------------------------------------------------------------------------
 # Coarse-to-fine retrieval: a cheap model shortlists k candidates per query, the cross-attention model scores only those pairs
-# (ops.scan_candidate_scores) and re-orders the shortlist (ops.rerank_lists).
+# (ops.scan_candidate_scores / ops.sgraf_candidate_scores) and re-orders the shortlist (ops.rerank_lists).
 def rerank_rank_vector(lists, coarse_ranks, direction, im_div=5):
     """Rank vector of the RERANKED ranking (host arithmetic, numpy only).  The reranked ranking of a query is its k shortlisted
     candidates in fine order followed by all other candidates in coarse order; the rank of a query is the best position of a
@@ -447,6 +447,30 @@ def rerank(sims_coarse, score_fn, k, im_div=5):
     return ops.recall_from_ranks(i_ranks), ops.recall_from_ranks(t_ranks), (i_ranks, t_ranks), lists
 
 
+def _packed_words(img_embs, cap_embs, cap_lens):
+    """encode_data's padded word-level embeddings -> (images, packed words, ScanPlan) on the current device"""
+    dev = torch.device('cuda', torch.cuda.current_device())
+    lens = np.asarray(cap_lens, dtype=np.int64)
+    images = torch.from_numpy(np.ascontiguousarray(img_embs)).to(dev)
+    caps = torch.from_numpy(np.ascontiguousarray(cap_embs)).to(dev)
+    L = caps.shape[1]
+    keep = (torch.arange(L, device=dev)[None, :] < torch.from_numpy(lens).to(dev)[:, None]).reshape(-1)
+    words = caps.reshape(-1, caps.shape[2])[keep].contiguous()
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    return images, words, ops.ScanPlan(off, lens.astype(np.int32), words.shape[0], dev)
+
+
+def _sgraf_score_fn(model, img_embs, cap_embs, cap_lens):
+    """score_fn of `rerank` for an SGRAF model (SAF or SGR): the captions packed once, the per-image / per-caption state (global
+    vectors, Gram matrices, SGR's folded weights) prepared once and used for both list directions."""
+    images, words, plan = _packed_words(img_embs, cap_embs, cap_lens)
+    enc = model.sim_enc
+    weights = {k_: v.detach() for k_, v in enc.state_dict().items()}
+    state = ops.sgraf_pairs_prepare(images, words, plan, weights, enc.module_name, enc.sgr_step)
+    return lambda cand, by: ops.sgraf_candidate_scores(images, words, plan, weights, cand, by, module_name=enc.module_name,
+                                                       sgr_step=enc.sgr_step, state=state)
+
+
 def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
     """score_fn of `rerank` for a SCAN model: its word-level caption embeddings packed once, the pair workspace prepared once."""
     cfg = model.config
@@ -467,7 +491,7 @@ def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
 
 def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split='dev', fold5=False):
     """Coarse-to-fine evaluation: the coarse model (any family evalrank_single scores) shortlists k candidates per query in both
-    directions, the fine model -- SCAN, either cross_attn -- scores only those pairs, Recall@K is that of the reranked ranking
+    directions, the fine model -- SCAN (either cross_attn) or SGRAF (SAF or SGR) -- scores only those pairs, Recall@K is that of the reranked ranking
     (`rerank`).  Writes `<data_name>[_5fold]_rerank<k>_result.yaml` (the coarse-only numbers under 'coarse', the reranked ones
     under 'rerank') and the reranked lists `<data_name>[_5fold]_rerank<k>.npz` next to the coarse checkpoint."""
     import os
@@ -477,9 +501,10 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
         raise ValueError("evalrank_rerank: k = %d < 10: R@10 would not be defined by the shortlist" % int(k))
     coarse, c_cfg = _load_for_eval(model_path_coarse, data_path)
     fine, f_cfg = _load_for_eval(model_path_fine, data_path)
-    if f_cfg['name'] != 'SCAN':
-        raise NotImplementedError("evalrank_rerank: the fine model must be SCAN (candidate-list scoring exists for SCAN only), got %s"
+    if f_cfg['name'] not in ('SCAN', 'SGRAF'):
+        raise NotImplementedError("evalrank_rerank: the fine model must be SCAN or SGRAF (candidate-list scoring exists for these only), got %s"
                                   % f_cfg['name'])
+    fine_score_fn = _scan_score_fn if f_cfg['name'] == 'SCAN' else _sgraf_score_fn
     if f_cfg['data_name'] != c_cfg['data_name']:
         raise ValueError("evalrank_rerank: the checkpoints name different datasets (%s, %s): their lists would not index the same items"
                          % (c_cfg['data_name'], f_cfg['data_name']))
@@ -496,7 +521,7 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
     def block(sl_img, sl_cap, prefix):
         sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
         res_c = cal_recall(sims)
-        fn = _scan_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
+        fn = fine_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
         r, ri, (i_ranks, t_ranks), tl = rerank(sims.astype(np.float32), fn, k)
         lists.update({prefix + key: v for key, v in tl.items()})
         res_r = _recall_dict((i_ranks, tl['i2t_topk'][:, 0], t_ranks, tl['t2i_topk'][:, 0]))

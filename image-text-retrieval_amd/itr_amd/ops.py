@@ -809,18 +809,19 @@ def _sgraf_workspace(lib, dev, Ni, Nc, n_rows, n_tiles, D, S_dim, mod, flags, im
         return ws, int(ib)
 
 
-def sgraf_scores(images, words, plan, weights, module_name='SAF', sgr_step=3, out=None, image_block=None, max_workspace_bytes=None,
-                 variant=()):
-    """EncoderSimilarity.forward (Fusionmodule.py:406-451), eval mode.  images (Ni, 36, D); words (n_rows, D)
-    with the caption layout of `plan` (ScanPlan on the WORD lengths); weights: the module's state_dict.
-    image_block / max_workspace_bytes: see _sgraf_workspace (default: the largest block the free memory admits).
-    variant: names from SGRAF_FLAGS -- the step-by-step / non-persistent forms the fused kernel is cross-checked against."""
-    lib = _lib.load()
-    if module_name not in ('SAF', 'SGR'):
-        raise ValueError('Invalid input of config.module_name in configs.py')
-    images = _dev(images, name="images")
-    words = _dev(words, name="words")
-    Ni, R, D = images.shape
+def _sgraf_weight_names(module_name, sgr_step):
+    """state_dict names of the tensors an EncoderSimilarity of this module reads"""
+    names = list(_SGRAF_MAP.values())
+    if module_name == 'SAF':
+        names += list(_SAF_MAP.values())
+    else:
+        for k in range(sgr_step):
+            names += ["SGR_module.sgr%d.%s.%s" % (k, m, t) for m in ("graph_query_w", "graph_key_w", "sim_graph_w") for t in ("weight", "bias")]
+    return names
+
+
+def _sgraf_weight_struct(weights, module_name, sgr_step):
+    """-> (itr_sgraf_weights struct of device pointers, the tensors that keep them alive, sim_dim)"""
     keep = []
     st = _lib.SgrafWeights()
 
@@ -841,6 +842,22 @@ def sgraf_scores(images, words, plan, weights, module_name='SAF', sgr_step=3, ou
             st.sgr_q_w[k] = ptr(pre + "graph_query_w.weight"); st.sgr_q_b[k] = ptr(pre + "graph_query_w.bias")
             st.sgr_k_w[k] = ptr(pre + "graph_key_w.weight"); st.sgr_k_b[k] = ptr(pre + "graph_key_w.bias")
             st.sgr_g_w[k] = ptr(pre + "sim_graph_w.weight"); st.sgr_g_b[k] = ptr(pre + "sim_graph_w.bias")
+    return st, keep, S_dim
+
+
+def sgraf_scores(images, words, plan, weights, module_name='SAF', sgr_step=3, out=None, image_block=None, max_workspace_bytes=None,
+                 variant=()):
+    """EncoderSimilarity.forward (Fusionmodule.py:406-451), eval mode.  images (Ni, 36, D); words (n_rows, D)
+    with the caption layout of `plan` (ScanPlan on the WORD lengths); weights: the module's state_dict.
+    image_block / max_workspace_bytes: see _sgraf_workspace (default: the largest block the free memory admits).
+    variant: names from SGRAF_FLAGS -- the step-by-step / non-persistent forms the fused kernel is cross-checked against."""
+    lib = _lib.load()
+    if module_name not in ('SAF', 'SGR'):
+        raise ValueError('Invalid input of config.module_name in configs.py')
+    images = _dev(images, name="images")
+    words = _dev(words, name="words")
+    Ni, R, D = images.shape
+    st, keep, S_dim = _sgraf_weight_struct(weights, module_name, sgr_step)
     mod = 0 if module_name == 'SAF' else 1
     flags = 0
     for v in ((variant,) if isinstance(variant, str) else variant):
@@ -1241,6 +1258,211 @@ def scan_candidate_scores(images, words, plan, cand, by, cross_attn='t2i', raw_f
         _NORMS[raw_feature_norm], _AGGS[agg_func], float(lambda_softmax), float(lambda_lse), _p(out), out.numel(), _p(ws), ws.numel(),
         _stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------ SGRAF on candidate lists
+def _sgraf_pairs_lens(plan, dev):
+    """Device copies of ALL captions' offsets and lengths for the SGRAF pair kernels; captions of more than SGRAF_MAX_WORDS words get
+    length 0 = "not scored by the kernels".  Cached on the plan."""
+    st = getattr(plan, "_sgraf_pairs_lens", None)
+    if st is None or st[0] != dev:
+        klen = np.where(plan.len_host > SGRAF_MAX_WORDS, 0, plan.len_host).astype(np.int32)
+        st = (dev, h2d(np.asarray(plan.off_host, dtype=np.int64), dev), h2d(klen, dev))
+        plan._sgraf_pairs_lens = st
+    return st[1], st[2]
+
+
+class SgrafPairsState:
+    """What `sgraf_pairs_prepare` computed and for what: the buffer (VisualSA / TextSA global vectors, the images' Gram matrices, SGR's
+    folded and packed weights) and the identity of the operands, the weights and the module.  `sgraf_candidate_scores` refuses a state
+    prepared for anything else.  The weights are identified by the CALLER's tensors (storage pointer and version counter of every
+    state_dict entry the module reads), so a state is reusable with the same dict -- or another dict of the same tensors, such as a
+    second `module.state_dict()` -- whatever copies the binding has to make of them."""
+
+    def __init__(self, buf, images, words, plan, weights, module_name, sgr_step, struct, keep, S_dim):
+        self.buf, self.plan, self.module_name, self.sgr_step = buf, plan, module_name, int(sgr_step)
+        self.struct, self.keep, self.S_dim = struct, keep, S_dim
+        self.key = self._key(images, words, weights, module_name, sgr_step)
+
+    @staticmethod
+    def _key(images, words, weights, module_name, sgr_step):
+        return ((tuple(images.shape), tuple(words.shape), images.data_ptr(), words.data_ptr(), images._version, words._version),
+                tuple((weights[n].data_ptr(), weights[n]._version, tuple(weights[n].shape)) for n in _sgraf_weight_names(module_name, int(sgr_step))))
+
+    def check(self, images, words, plan, weights, module_name, sgr_step):
+        if self.module_name != module_name or (module_name == 'SGR' and self.sgr_step != int(sgr_step)):
+            raise ValueError("sgraf_candidate_scores: state was prepared for module %r (%d steps), called with %r (%d steps)"
+                             % (self.module_name, self.sgr_step, module_name, int(sgr_step)))
+        if self.plan is not plan or self.key != self._key(images, words, weights, module_name, sgr_step):
+            raise ValueError("sgraf_candidate_scores: state was prepared for other images, words, plan or weights (or they were modified since)")
+
+
+def sgraf_pairs_prepare(images, words, plan, weights, module_name='SAF', sgr_step=3):
+    """Per image set / caption set / weights precompute of `sgraf_candidate_scores`: once per image and caption, never per pair or per
+    chunk.  -> SgrafPairsState, valid for these images, words, plan, weights and module only."""
+    lib = _lib.load()
+    if module_name not in ('SAF', 'SGR'):
+        raise ValueError('Invalid input of config.module_name in configs.py')
+    images = _dev(images, name="images")
+    words = _dev(words, name="words")
+    Ni, R, D = images.shape
+    if R != SCAN_R:
+        raise NotImplementedError("sgraf_pairs_prepare: %d regions per image (VisualSA is built for %d)" % (R, SCAN_R))
+    if plan.Nc and int(plan.len_host.max()) > SGRAF_COMPOSED_MAX_WORDS:
+        raise NotImplementedError("sgraf_candidate_scores: captions of at most %d words are supported" % SGRAF_COMPOSED_MAX_WORDS)
+    st, keep, S_dim = _sgraf_weight_struct(weights, module_name, sgr_step)
+    mod = 0 if module_name == 'SAF' else 1
+    off, klen = _sgraf_pairs_lens(plan, images.device)
+    nb = lib.itr_sgraf_pairs_state_bytes(Ni, plan.Nc, words.shape[0], D, S_dim, mod, int(sgr_step))
+    buf = torch.empty(max(nb, 1), device=images.device, dtype=torch.uint8)
+    sb = lib.itr_sgraf_pairs_prepare_scratch_bytes(Ni, plan.Nc, words.shape[0], D, S_dim, mod)
+    scratch = torch.empty(max(sb, 1), device=images.device, dtype=torch.uint8)       # the global nodes' intermediates: freed on return
+    _lib.check(lib.itr_sgraf_pairs_prepare(_p(images), _p(words), _p(off), _p(klen), Ni, plan.Nc, words.shape[0], R, D, S_dim, mod, int(sgr_step),
+                                           C.byref(st), _p(buf), nb, _p(scratch), sb, _stream()))
+    del scratch
+    return SgrafPairsState(buf, images, words, plan, weights, module_name, sgr_step, st, keep, S_dim)
+
+
+SGRAF_PAIRS_LAST = {}          # diagnostics: chunks, items and workspace of the last sgraf_candidate_scores call
+
+
+def sgraf_candidate_scores(images, words, plan, weights, cand, by, module_name='SAF', sgr_step=3, max_workspace_bytes=None, state=None):
+    """SGRAF scores (EncoderSimilarity.forward, Fusionmodule.py:406-451, eval mode) of candidate lists only -- the fine stage of
+    coarse-to-fine retrieval.  With S the matrix `sgraf_scores` would return:
+      by='caption': cand int32 [Nc, K] image indices   -> [Nc, K], out[c, k] = S[cand[c, k], c]
+      by='image':   cand int32 [Ni, K] caption indices -> [Ni, K], out[i, k] = S[i, cand[i, k]]
+    Only the listed pairs are computed (csrc/sgraf_pairs.hip), each to the same bits whatever else is listed, in any order, at any K,
+    through either `by`, under any workspace budget.  Duplicates inside a list are allowed; any K >= 1; an empty dimension gives an
+    empty result.  Captions of 64..191 words are scored by the per-caption composition of the training path on their listed images
+    (correct, not fast).  The pairs are processed in chunks sized to `max_workspace_bytes` (default: 90 % of free + cached device
+    memory).  `state`: sgraf_pairs_prepare's, to reuse the per-image / per-caption work across calls (both list directions).
+    Pairs per call: the contract's refusal is at 2^31; the item plan indexes columns as 64 x item in int32, so lists of 2^31 / 64 =
+    33 554 432 pairs or more are refused as well (NotImplementedError: split the lists)."""
+    lib = _lib.load()
+    if module_name not in ('SAF', 'SGR'):
+        raise ValueError('Invalid input of config.module_name in configs.py')
+    if by not in ('caption', 'image'):
+        raise ValueError("sgraf_candidate_scores: by must be 'caption' or 'image', got %r" % (by,))
+    images = _dev(images, name="images")
+    words = _dev(words, name="words")
+    if not torch.is_tensor(cand) or not cand.is_cuda or cand.dtype != torch.int32:
+        _dev(cand, torch.int32, name="cand")                      # (raises; a view is made contiguous only after the shape checks)
+    if cand.dim() != 2:
+        raise ValueError("sgraf_candidate_scores: cand must be 2-D, got shape %s" % (tuple(cand.shape),))
+    Ni, R, D = images.shape
+    Nc = plan.Nc
+    dev = images.device
+    n_q, n_t = (Nc, Ni) if by == 'caption' else (Ni, Nc)
+    if cand.shape[0] != n_q:
+        raise ValueError("sgraf_candidate_scores: by=%r needs %d lists, got %d" % (by, n_q, cand.shape[0]))
+    K = cand.shape[1]
+    if n_q * K >= 2 ** 31 // 64:
+        raise NotImplementedError("sgraf_candidate_scores: %d pairs (at most %d per call); split the lists" % (n_q * K, 2 ** 31 // 64 - 1))
+    cand = cand.contiguous()
+    out = torch.empty(n_q, K, device=dev, dtype=torch.float32)
+    if state is not None:
+        if not isinstance(state, SgrafPairsState):
+            raise TypeError("sgraf_candidate_scores: state must come from sgraf_pairs_prepare")
+        state.check(images, words, plan, weights, module_name, sgr_step)
+    if n_q == 0 or K == 0:
+        return out
+    if R != SCAN_R:
+        raise NotImplementedError("sgraf_candidate_scores: %d regions per image (VisualSA is built for %d)" % (R, SCAN_R))
+    if len(plan.len_host) and int(plan.len_host.max()) > SGRAF_COMPOSED_MAX_WORDS:
+        raise NotImplementedError("sgraf_candidate_scores: captions of at most %d words are supported" % SGRAF_COMPOSED_MAX_WORDS)
+    lo, hi = torch.aminmax(cand)
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi >= n_t:
+        raise ValueError("sgraf_candidate_scores: candidate index out of range [0, %d): min %d, max %d" % (n_t, lo, hi))
+    if state is None:
+        state = sgraf_pairs_prepare(images, words, plan, weights, module_name, sgr_step)
+    S_dim, st = state.S_dim, state.struct
+    mod = 0 if module_name == 'SAF' else 1
+    # ---- image-major (CSR) form, on the device: no dense intermediate
+    flat = cand.reshape(-1).to(torch.int64)
+    qid = torch.arange(n_q, device=dev, dtype=torch.int64).repeat_interleave(K)
+    caps, imgs = (qid, flat) if by == 'caption' else (flat, qid)
+    slot = torch.arange(n_q * K, device=dev, dtype=torch.int64)
+    if len(plan.len_host) and int(plan.len_host.max()) > SGRAF_MAX_WORDS:
+        is_long = h2d(plan.len_host > SGRAF_MAX_WORDS, dev)
+        lm = is_long[caps]
+        _sgraf_long_caption_pairs(images, words, plan, weights, module_name, sgr_step, S_dim, caps[lm], imgs[lm], slot[lm], out)
+        caps, imgs, slot = caps[~lm], imgs[~lm], slot[~lm]
+    if by == 'caption' and caps.numel():
+        imgs, order = torch.sort(imgs, stable=True)
+        caps, slot = caps[order], slot[order]
+    P = caps.numel()
+    if P == 0:
+        return out
+    img_ptr = torch.zeros(Ni + 1, device=dev, dtype=torch.int32)
+    img_ptr[1:] = torch.cumsum(torch.bincount(imgs, minlength=Ni), 0).to(torch.int32)
+    pair_img, pair_cap, pair_out = imgs.to(torch.int32), caps.to(torch.int32), slot.to(torch.int32)
+    off, klen = _sgraf_pairs_lens(plan, dev)
+    pair_len, pair_col, pair_capok = (torch.empty(P, device=dev, dtype=torch.int32) for _ in range(3))
+    item_begin = torch.empty(P + 1, device=dev, dtype=torch.int32)
+    item_img = torch.empty(P, device=dev, dtype=torch.int32)
+    n_items_dev = torch.zeros(1, device=dev, dtype=torch.int32)
+    pwb = lib.itr_sgraf_pairs_plan_workspace_bytes(Ni)
+    pws = torch.empty(max(pwb, 1), device=dev, dtype=torch.uint8)
+    _lib.check(lib.itr_sgraf_pairs_plan(_p(img_ptr), _p(pair_cap), _p(off), _p(klen), P, Ni, Nc, words.shape[0], _p(pair_len), _p(pair_col),
+                                        _p(pair_capok), _p(item_begin), _p(item_img), _p(n_items_dev), _p(pws), pwb, _stream()))
+    n_items = int(n_items_dev)                                  # (the one host read-back of the plan: chunk bounds need it)
+    ib = item_begin[:n_items + 1].cpu().numpy().astype(np.int64)
+    # ---- chunks of whole items sized to the budget
+    if max_workspace_bytes is None:
+        free, _total = torch.cuda.mem_get_info(dev)
+        cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        budget = int(0.9 * (free + cached))
+    else:
+        budget = int(max_workspace_bytes)
+
+    def need(it0, it1):
+        return lib.itr_sgraf_pair_scores_workspace_bytes(int(ib[it1] - ib[it0]), it1 - it0, D, S_dim, mod, int(sgr_step))
+
+    chunks, it0 = [], 0
+    while it0 < n_items:
+        if need(it0, it0 + 1) > budget:
+            raise torch.cuda.OutOfMemoryError("sgraf_candidate_scores: one item needs %d bytes of workspace, %d allowed" % (need(it0, it0 + 1), budget))
+        lo_, hi_ = it0 + 1, n_items                             # the largest it1 whose chunk fits (need is monotone)
+        while lo_ < hi_:
+            mid = (lo_ + hi_ + 1) // 2
+            if need(it0, mid) <= budget:
+                lo_ = mid
+            else:
+                hi_ = mid - 1
+        chunks.append((it0, lo_))
+        it0 = lo_
+    wsb = max(need(a, b) for a, b in chunks)
+    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+    SGRAF_PAIRS_LAST.update(pairs=P, items=n_items, chunks=len(chunks), workspace_bytes=int(wsb), budget_bytes=budget)
+    for a, b in chunks:
+        _lib.check(lib.itr_sgraf_pair_scores(_p(images), _p(words), _p(off), _p(pair_img), _p(pair_capok), _p(pair_len), _p(pair_col), _p(pair_out),
+                                             _p(item_begin), _p(item_img), int(ib[a]), int(ib[b] - ib[a]), a, b - a, Ni, Nc, words.shape[0], R, D,
+                                             S_dim, mod, int(sgr_step), C.byref(st), _p(state.buf), state.buf.numel(), _p(out), out.numel(),
+                                             _p(ws), wsb, _stream()))
+    return out
+
+
+def _sgraf_long_caption_pairs(images, words, plan, weights, module_name, sgr_step, S_dim, caps, imgs, slot, out):
+    """Listed pairs of captions with 64..191 words: Fusionmodule.encoder_similarity_train(training=False) -- what sgraf_scores runs for
+    such captions -- on each caption's listed images, then a gather into the lists' slots."""
+    if caps.numel() == 0:
+        return
+    from .modalmodule import Fusionmodule
+    D = images.shape[2]
+    sim_enc = Fusionmodule.EncoderSimilarity(D, S_dim, module_name, sgr_step)
+    own = sim_enc.state_dict()
+    sim_enc.load_state_dict({k: (weights[k].detach() if k in weights else own[k]) for k in own if k in weights or k.endswith('num_batches_tracked')})
+    sim_enc.to(images.device).eval()
+    flat = out.view(-1)
+    with torch.no_grad():
+        for c in torch.unique(caps).tolist():
+            m = caps == c
+            sel, inv = torch.unique(imgs[m], return_inverse=True)
+            o, l = int(plan.off_host[c]), int(plan.len_host[c])
+            col = Fusionmodule.encoder_similarity_train(sim_enc, images[sel].contiguous(), words[o:o + l].contiguous(), np.zeros(1, np.int64), [l],
+                                                        None, training=False)
+            flat[slot[m]] = col.reshape(-1)[inv]
 
 
 def _scan_long_caption_pairs(images, words, plan, caps, imgs, slot, out, cross_attn, norm, agg, lambda_lse, lambda_softmax):

@@ -3,7 +3,7 @@
 [--split test|testall|dev] [--fold5] [--topk K] [--rerank K]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
 (and with --topk K the top-K retrieval lists of every query in <data_name>[_5fold]_{single,ensemble}_top<K>.npz).
 python test.py COARSE_PATH FINE_PATH --rerank K: coarse-to-fine retrieval, the first model shortlists K candidates per query and the
-second (SCAN) scores only those  ->  <data_name>[_5fold]_rerank<K>_result.yaml and <data_name>[_5fold]_rerank<K>.npz"""
+second (SCAN or SGRAF) scores only those  ->  <data_name>[_5fold]_rerank<K>_result.yaml and <data_name>[_5fold]_rerank<K>.npz"""
 import argparse
 import os
 import sys
@@ -22,7 +22,7 @@ if __name__ == "__main__":
     ap.add_argument("--topk", type=int, default=0, metavar="K",
                     help="also write the top-K retrieved items of every query (indices and scores) to <data_name>..._top<K>.npz")
     ap.add_argument("--rerank", type=int, default=0, metavar="K",
-                    help="two checkpoints COARSE FINE: FINE (SCAN) re-scores only COARSE's top-K candidates of every query")
+                    help="two checkpoints COARSE FINE: FINE (SCAN or SGRAF) re-scores only COARSE's top-K candidates of every query")
     a = ap.parse_args()
     if a.rerank:
         if len(a.model_path) != 2:

@@ -36,7 +36,7 @@ typedef void *itr_stream_t;
 
 const char *itr_last_error(void);
 /* ABI version, bumped on any signature change. */
-#define ITR_ABI_VERSION 33
+#define ITR_ABI_VERSION 34
 int itr_abi_version(void);
 
 /* ---- a1: l2norm / l1norm  (itr/modalmodule/utils.py:4-15) ----------------------------
@@ -418,6 +418,43 @@ int itr_scan_pair_scores(const float *img, const float *words, const int64_t *ca
                          int64_t Nc, int64_t n_rows, int R, int D, int mode, int norm, int agg, float lambda_softmax,
                          float lambda_lse, float *out, int64_t out_len, void *workspace, size_t workspace_bytes,
                          itr_stream_t stream);
+/* ---- a7 on candidate lists: EncoderSimilarity.forward (Fusionmodule.py:406-451, with VisualSA :491-507, TextSA :543-559,
+ * SCAN_attention :632-664, AttentionFiltration :615-619, GraphReasoning :581-587) for LISTED (image, caption) pairs ----
+ * Only the listed pairs are scored (csrc/sgraf_pairs.hip); no (Ni, Nc) intermediate exists.  A pair's score depends on that pair
+ * alone: the same bits in any list, order, chunk or direction.  Operands, weights, module and limits as itr_sgraf_scores
+ * (R = 36, D % 32 == 0, S <= 1024, captions of 1..63 words; cap_len[c] == 0 marks a caption that is not scored here).
+ *
+ * itr_sgraf_pairs_prepare fills `state` (itr_sgraf_pairs_state_bytes) ONCE per image set, caption set, weights and module: the
+ *   VisualSA / TextSA global vectors, the images' Gram matrices, SGR's folded and fragment-ordered weights.  `scratch`
+ *   (itr_sgraf_pairs_prepare_scratch_bytes) holds its intermediates and is free again when the call has run.
+ * itr_sgraf_pairs_plan turns an IMAGE-major list (CSR: the pairs of image i are p in [img_ptr[i], img_ptr[i + 1]), pair p is
+ *   (image i, caption pair_cap[p])) into items of one image x whole captions (<= 16 captions, words + captions <= 64), on the
+ *   device (P < 2^31 / 64 = 33 554 432 pairs per call, ITR_ERR_UNSUPPORTED above: a column index is 64 x the item index in int32):
+ *   pair_len[P], pair_col[P] (first column of the pair's words, 64 columns per item), pair_capok[P] (the caption, or -1
+ *   for a pair that cannot be scored: its score is NaN), item_begin[n_items + 1] (first pair; the buffer holds P + 1 entries),
+ *   item_img[n_items] (buffer: P entries) and n_items_dev[0] = n_items.  workspace: itr_sgraf_pairs_plan_workspace_bytes(Ni).
+ * itr_sgraf_pair_scores scores the chunk of pairs [p0, p0 + n_pairs) = items [it0, it0 + n_items) (whole items: p0 ==
+ *   item_begin[it0], p0 + n_pairs == item_begin[it0 + n_items]) and writes out[pair_out[p]] (a slot outside [0, out_len) is
+ *   skipped).  pair_img[P] is the image of every pair.  workspace: itr_sgraf_pair_scores_workspace_bytes(n_pairs, n_items, ...),
+ *   monotone in both counts: the caller sizes chunks to the memory it has. */
+size_t itr_sgraf_pairs_state_bytes(int64_t Ni, int64_t Nc, int64_t n_rows, int D, int S, int module, int sgr_step);
+int itr_sgraf_pairs_prepare(const float *img, const float *words, const int64_t *cap_off, const int32_t *cap_len, int64_t Ni,
+                            int64_t Nc, int64_t n_rows, int R, int D, int S, int module, int sgr_step,
+                            const itr_sgraf_weights *w, void *state, size_t state_bytes, void *scratch, size_t scratch_bytes,
+                            itr_stream_t stream);
+size_t itr_sgraf_pairs_prepare_scratch_bytes(int64_t Ni, int64_t Nc, int64_t n_rows, int D, int S, int module);
+size_t itr_sgraf_pairs_plan_workspace_bytes(int64_t Ni);
+int itr_sgraf_pairs_plan(const int32_t *img_ptr, const int32_t *pair_cap, const int64_t *cap_off, const int32_t *cap_len, int64_t P,
+                         int64_t Ni, int64_t Nc, int64_t n_rows, int32_t *pair_len, int32_t *pair_col, int32_t *pair_capok,
+                         int32_t *item_begin, int32_t *item_img, int32_t *n_items_dev, void *workspace, size_t workspace_bytes,
+                         itr_stream_t stream);
+size_t itr_sgraf_pair_scores_workspace_bytes(int64_t n_pairs, int64_t n_items, int D, int S, int module, int sgr_step);
+int itr_sgraf_pair_scores(const float *img, const float *words, const int64_t *cap_off, const int32_t *pair_img,
+                          const int32_t *pair_capok, const int32_t *pair_len, const int32_t *pair_col, const int32_t *pair_out,
+                          const int32_t *item_begin, const int32_t *item_img, int64_t p0, int64_t n_pairs, int64_t it0,
+                          int64_t n_items, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D, int S, int module, int sgr_step,
+                          const itr_sgraf_weights *w, const void *state, size_t state_bytes, float *out, int64_t out_len,
+                          void *workspace, size_t workspace_bytes, itr_stream_t stream);
 /* Re-order n lists of K candidates by new scores (evaluation.py:169, :209: the order np.argsort(...)[::-1] gives these K
  * candidates): idx [n, K] candidates, val [n, K] their new scores -> idx_out / val_out in the ranker's order (larger score
  * first, the higher index on exact ties, -0.0 == +0.0, NaN as +inf; of two entries with the same candidate and score the one

@@ -33,6 +33,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.environ.get("ITR_CSRC", os.path.join(ROOT, "image-text-retrieval_amd", "csrc"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
+# Kernels added after tests/test_isa_audit.py's list was written: besides being clean, they must be PRESENT in their source's audit (a
+# kernel that lost its asm loads, or its name, would otherwise drop out silently).  main() and audit_file(require_listed=True) enforce it.
+AUDITED_KERNELS = {
+    "sgraf_loc.hip": ["sgraf_loc_items_kernel"],       # the candidate-list form of sgraf_loc_kernel (sgraf_pairs.hip)
+}
+
 _REG = re.compile(r"\bv\[(\d+):(\d+)\]|\bv(\d+)\b")
 
 
@@ -244,7 +250,7 @@ def audit_kernel(name, lines, no_scratch_in_loops=False):
     return out
 
 
-def audit_file(src, kernel_filter=None, no_scratch_in_loops=False, keep=None):
+def audit_file(src, kernel_filter=None, no_scratch_in_loops=False, keep=None, require_listed=False):
     with tempfile.TemporaryDirectory() as tmp:
         asm = compile_to_asm(os.path.abspath(src), tmp)
         if keep:
@@ -257,6 +263,10 @@ def audit_file(src, kernel_filter=None, no_scratch_in_loops=False, keep=None):
             r = audit_kernel(name, lines, no_scratch_in_loops)
             if r is not None:
                 results[name] = r
+        if require_listed and not kernel_filter:
+            for k in AUDITED_KERNELS.get(os.path.basename(src), []):
+                if not any(k in name for name in results):
+                    results[k] = ["listed in AUDITED_KERNELS but not found in %s (or it no longer contains asm loads)" % os.path.basename(src)]
         return results
 
 
@@ -267,7 +277,7 @@ def main():
     ap.add_argument("--no-scratch-in-loops", action="store_true")
     ap.add_argument("--keep-asm", default=None)
     a = ap.parse_args()
-    res = audit_file(a.source, a.kernel, a.no_scratch_in_loops, a.keep_asm)
+    res = audit_file(a.source, a.kernel, a.no_scratch_in_loops, a.keep_asm, require_listed=True)
     bad = 0
     for name, rep in res.items():
         print("%s: %s" % (name, "clean" if not rep else "%d finding(s)" % len(rep)))
