@@ -37,17 +37,12 @@
 // Limits: R = 36, D % 16 == 0, captions of 1..64 words (cap_len 0 = "not scored here": ops routes 65..96 words elsewhere).
 // Index hygiene: an image index outside [0, Ni), a caption length outside 1..64 or an output slot outside [0, out_len) is never
 // dereferenced; the pair's score is NaN (bad image / length) or dropped (bad slot).
-#include <type_traits>
-
-#include "scan_common.h"
-#include "itr_internal.h"
-#include "pair_mainloop.h"
+#include "pair_epilogue.h"
 
 namespace itr {
 
 constexpr int SP_IMGS = 8;                 // pairs (= waves) per workgroup
 constexpr int SP_THREADS = SP_IMGS * 64;
-constexpr int SP_MAXW = 64;                // words per caption
 
 struct PairArgs {
     const float *img;            // [Ni, 36, D]
@@ -76,46 +71,6 @@ struct PairSmem {
 constexpr size_t SP_LDS_T2I = sizeof(PairSmem);
 constexpr size_t SP_LDS_I2T = sizeof(PairSmem) + SP_MAXW * SP_MAXW * 4;
 static_assert(SP_LDS_I2T <= 160 * 1024, "a workgroup's LDS must fit one CU (one workgroup per CU in both modes: header)");
-
-// statistics of the first normalisation (Objectives.py:436-457) along one group, NORM a compile-time constant
-template <int NORM>
-struct PairNorm {
-    float s0, s1;
-    __device__ __forceinline__ void init() { s0 = (NORM == 2) ? -INFINITY : 0.f; s1 = 0.f; }
-    __device__ __forceinline__ void pass1(float a) {
-        if (NORM == 0) { const float b = leaky(a); s0 = fmaf(b, b, s0); }
-        else if (NORM == 1) s0 = fmaf(a, a, s0);
-        else if (NORM == 2) s0 = fmaxf(s0, a);
-        else if (NORM == 5) s0 += fabsf(a);
-        else if (NORM == 6) s0 += fabsf(leaky(a));
-    }
-    __device__ __forceinline__ void pass2(float a) { if (NORM == 2) s1 += fast_exp(a - s0); }
-    __device__ __forceinline__ void finish() {
-        if (NORM == 0 || NORM == 1) s0 = 1.f / (sqrtf(s0) + 1e-8f);
-        else if (NORM == 5 || NORM == 6) s0 = 1.f / (s0 + 1e-8f);
-        else if (NORM == 2) s1 = 1.f / s1;
-    }
-    static __device__ __forceinline__ float apply(float a, float t0, float t1) {
-        if (NORM == 0 || NORM == 6) return leaky(a) * t0;
-        if (NORM == 1 || NORM == 5) return a * t0;
-        if (NORM == 2) return fast_exp(a - t0) * t1;
-        if (NORM == 4) return leaky(a);
-        return a;
-    }
-};
-
-template <typename F>
-__device__ __forceinline__ void pair_dispatch_norm(int norm, F &&f) {
-    switch (norm) {
-        case 0: f(std::integral_constant<int, 0>{}); break;
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 5: f(std::integral_constant<int, 5>{}); break;
-        default: f(std::integral_constant<int, 6>{}); break;
-    }
-}
 
 __device__ __forceinline__ float pair_aggregate(float sim, bool on, int n, int agg, float ll) {
     float r;
@@ -311,37 +266,6 @@ __global__ __launch_bounds__(1024) void pairs_blkptr_kernel(const int32_t *__res
     __syncthreads();
     int run = part[t];
     for (int64_t i = b; i < e; ++i) { blk_ptr[i] = run; run += blocks(i); }
-}
-
-struct PairWs {
-    int32_t *blk_ptr;
-    float *gram, *wnorm, *vnorm, *cgram;
-    int64_t *coff;
-    size_t bytes;
-};
-static PairWs pair_ws(void *base, int64_t Ni, int R, int64_t n_rows, int64_t Nc, int mode) {
-    WsCarver c(base);
-    PairWs w{};
-    w.blk_ptr = c.take<int32_t>((size_t)(Nc + 1) * 4);
-    if (mode == 0) {
-        w.gram = c.take<float>((size_t)Ni * R * R * 4);
-        w.wnorm = c.take<float>((size_t)n_rows * 4);
-    } else {
-        w.vnorm = c.take<float>((size_t)Ni * R * 4);
-        w.coff = c.take<int64_t>((size_t)Nc * 8);
-        w.cgram = c.take<float>((size_t)n_rows * SP_MAXW * 4);
-    }
-    w.bytes = c.bytes;
-    return w;
-}
-
-static int pair_check_shape(const char *who, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D, int mode) {
-    ITR_REQUIRE(Ni >= 0 && Nc >= 0 && n_rows >= 0, "%s: bad shape", who);
-    ITR_REQUIRE(Nc < 0x7fffffffLL && Ni < 0x7fffffffLL, "%s: index overflow", who);
-    if (mode != 0 && mode != 1) { set_error("unknown cross_attn mode %d", mode); return ITR_ERR_BADARG; }
-    ITR_UNSUPPORTED(R != SC_R, "%s: this build handles %d regions per image, got %d", who, SC_R, R);
-    ITR_UNSUPPORTED(D <= 0 || D % SP_BK != 0, "%s: embed dim must be a multiple of %d, got %d", who, SP_BK, D);
-    return ITR_OK;
 }
 
 }  // namespace itr

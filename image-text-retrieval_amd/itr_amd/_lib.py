@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libitr_hip.so")
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 i32, i64, f32, vp, sz, u64 = C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_uint64
 
@@ -120,6 +120,8 @@ SIGNATURES = {
     "itr_sgraf_pair_scores": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, sz,
                                     vp, i64, vp, sz, vp]),
     "itr_scan_pair_scores": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, f32, f32, vp, i64, vp, sz, vp]),
+    "itr_scan_pair_attention": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, i64, vp, vp, i64,
+                                      vp, vp, sz, vp]),
     "itr_rerank_lists": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     # ---- training step
     "itr_l2norm_fwd_save": (i32, [vp, vp, vp, i64, i32, f32, vp]),

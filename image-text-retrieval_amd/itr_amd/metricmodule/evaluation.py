@@ -447,6 +447,36 @@ def rerank(sims_coarse, score_fn, k, im_div=5):
     return ops.recall_from_ranks(i_ranks), ops.recall_from_ranks(t_ranks), (i_ranks, t_ranks), lists
 
 
+def explain(lists, score_fn, m):
+    """Why the fine model preferred a result: the word-by-region attention of the best `m` results of every query in both
+    directions.  lists: `rerank`'s (reranked) lists; score_fn: a fine scorer that can explain (`_scan_score_fn`'s: SCAN); 1 <= m <= k.
+    -> dict of host arrays, per direction d in ('i2t', 't2i'): d_idx int64 [n, m] (query-major: the first m columns of d_topk),
+    d_scores float32 [n, m] (fine scores), d_attn float32 (flat; pair q * m + j holds its [W, 36] word-major block at d_attn_ptr),
+    d_attn_ptr int64 [n m + 1], d_row_sim (t2i model: one cosine per word at d_row_ptr; i2t model: 36 per pair), d_row_ptr int64
+    [n m + 1], d_cap_len int32 [n m].  With the data layer's `boxes`, region r of d_attn's column r is the box to draw."""
+    attention = getattr(score_fn, 'attention', None)
+    if attention is None:
+        raise NotImplementedError("explain: attention maps exist for a SCAN fine model only")
+    m = int(m)
+    out = {}
+    for d, by in (('i2t', 'image'), ('t2i', 'caption')):
+        idx = np.asarray(lists[d + '_topk'])
+        if m < 1 or m > idx.shape[1]:
+            raise ValueError("explain: m = %d outside [1, %d]" % (m, idx.shape[1]))
+        dev = torch.device('cuda', torch.cuda.current_device())
+        cand = torch.from_numpy(np.ascontiguousarray(idx[:, :m]).astype(np.int32)).to(dev)
+        a = attention(cand, by, m)
+        n = idx.shape[0]
+        out.update({d + '_idx': idx[:, :m].astype(np.int64), d + '_scores': a.score.cpu().numpy().reshape(n, m),
+                    d + '_attn': a.attn.cpu().numpy(), d + '_attn_ptr': a.attn_ptr.cpu().numpy(),
+                    d + '_row_sim': a.row_sim.cpu().numpy(), d + '_row_ptr': a.row_ptr.cpu().numpy(),
+                    d + '_cap_len': a.cap_len.cpu().numpy()})
+    return out
+
+
+_explain_lists = explain          # evalrank_rerank's keyword `explain` hides the function there
+
+
 def _packed_words(img_embs, cap_embs, cap_lens):
     """encode_data's padded word-level embeddings -> (images, packed words, ScanPlan) on the current device"""
     dev = torch.device('cuda', torch.cuda.current_device())
@@ -472,7 +502,8 @@ def _sgraf_score_fn(model, img_embs, cap_embs, cap_lens):
 
 
 def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
-    """score_fn of `rerank` for a SCAN model: its word-level caption embeddings packed once, the pair workspace prepared once."""
+    """score_fn of `rerank` for a SCAN model: its word-level caption embeddings packed once, the pair workspace prepared once.
+    Its attribute `attention(cand, by, m)` is ops.scan_candidate_attention on the same operands and workspace (`explain`)."""
     cfg = model.config
     dev = torch.device('cuda', torch.cuda.current_device())
     lens = np.asarray(cap_lens, dtype=np.int64)
@@ -486,24 +517,38 @@ def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
     kw = dict(cross_attn=cfg['cross_attn'], raw_feature_norm=cfg['raw_feature_norm'], agg_func=cfg['agg_func'],
               lambda_lse=cfg['lambda_lse'], lambda_softmax=cfg['lambda_softmax'])
     ws = ops.scan_pairs_prepare(images, words, plan, cfg['cross_attn'])
-    return lambda cand, by: ops.scan_candidate_scores(images, words, plan, cand, by, workspace=ws, **kw)
+
+    def fn(cand, by):
+        return ops.scan_candidate_scores(images, words, plan, cand, by, workspace=ws, **kw)
+    fn.attention = lambda cand, by, m: ops.scan_candidate_attention(images, words, plan, cand, by, m=m, workspace=ws, **kw)
+    return fn
 
 
-def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split='dev', fold5=False):
+def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split='dev', fold5=False, explain=None):
     """Coarse-to-fine evaluation: the coarse model (any family evalrank_single scores) shortlists k candidates per query in both
     directions, the fine model -- SCAN (either cross_attn) or SGRAF (SAF or SGR) -- scores only those pairs, Recall@K is that of the reranked ranking
     (`rerank`).  Writes `<data_name>[_5fold]_rerank<k>_result.yaml` (the coarse-only numbers under 'coarse', the reranked ones
-    under 'rerank') and the reranked lists `<data_name>[_5fold]_rerank<k>.npz` next to the coarse checkpoint."""
+    under 'rerank') and the reranked lists `<data_name>[_5fold]_rerank<k>.npz` next to the coarse checkpoint.
+    explain=M (1 <= M <= k, SCAN fine model, not with fold5): after re-ordering, the best M results of every query in both
+    directions are explained (`explain`) and written to `<data_name>_rerank<k>_explain<M>.npz` next to the other files."""
     import os
     import yaml
     from ..datamodule import data_loader as data
     if int(k) < 10:
         raise ValueError("evalrank_rerank: k = %d < 10: R@10 would not be defined by the shortlist" % int(k))
+    explain_m = None if explain is None else int(explain)
+    if explain_m is not None:
+        if fold5:
+            raise ValueError("evalrank_rerank: explain does not combine with fold5")
+        if explain_m < 1 or explain_m > int(k):
+            raise ValueError("evalrank_rerank: explain = %d outside [1, k = %d]" % (explain_m, int(k)))
     coarse, c_cfg = _load_for_eval(model_path_coarse, data_path)
     fine, f_cfg = _load_for_eval(model_path_fine, data_path)
     if f_cfg['name'] not in ('SCAN', 'SGRAF'):
         raise NotImplementedError("evalrank_rerank: the fine model must be SCAN or SGRAF (candidate-list scoring exists for these only), got %s"
                                   % f_cfg['name'])
+    if explain_m is not None and f_cfg['name'] != 'SCAN':
+        raise NotImplementedError("evalrank_rerank: explain needs a SCAN fine model (attention maps exist for SCAN only), got %s" % f_cfg['name'])
     fine_score_fn = _scan_score_fn if f_cfg['name'] == 'SCAN' else _sgraf_score_fn
     if f_cfg['data_name'] != c_cfg['data_name']:
         raise ValueError("evalrank_rerank: the checkpoints name different datasets (%s, %s): their lists would not index the same items"
@@ -516,7 +561,7 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
     if len(c_img) != len(f_img) or len(c_cap) != len(f_cap):
         raise ValueError("evalrank_rerank: the two models' loaders hold different item counts (%d / %d images, %d / %d captions)"
                          % (len(c_img), len(f_img), len(c_cap), len(f_cap)))
-    lists = {}
+    lists, explained = {}, {}
 
     def block(sl_img, sl_cap, prefix):
         sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
@@ -524,6 +569,8 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
         fn = fine_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
         r, ri, (i_ranks, t_ranks), tl = rerank(sims.astype(np.float32), fn, k)
         lists.update({prefix + key: v for key, v in tl.items()})
+        if explain_m is not None:
+            explained.update(_explain_lists(tl, fn, explain_m))
         res_r = _recall_dict((i_ranks, tl['i2t_topk'][:, 0], t_ranks, tl['t2i_topk'][:, 0]))
         print("Reranked (k = %d) image to text: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((k,) + tuple(r)))
         print("Reranked (k = %d) text to image: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((k,) + tuple(ri)))
@@ -549,4 +596,6 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
     with open(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_result.yaml'), 'w') as f:
         yaml.safe_dump(_plain(res_dic), f)
     np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}.npz'), **lists)
+    if explain_m is not None:
+        np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_explain{explain_m}.npz'), **explained)
     return res_dic

@@ -1260,6 +1260,135 @@ def scan_candidate_scores(images, words, plan, cand, by, cross_attn='t2i', raw_f
     return out
 
 
+# ------------------------------------------------------------------------------------------ SCAN attention maps of listed pairs
+class ScanPairAttention:
+    """What `scan_pair_attention` returns for P pairs: `attn` float32 (flat; pair p holds its [W_p, 36] row-major block at
+    attn_ptr[p]), `attn_ptr` int64 [P + 1], `row_sim` float32 (t2i: W_p cosines per pair at row_ptr[p]; i2t: 36 per pair at
+    36 p), `row_ptr` int64 [P + 1], `score` float32 [P], `cap_len` int32 [P] (W_p), all on the device, and `pairs` int32 [P, 2]."""
+
+    def __init__(self, pairs, attn, attn_ptr, row_sim, row_ptr, score, cap_len, cross_attn):
+        self.pairs, self.attn, self.attn_ptr, self.row_sim, self.row_ptr = pairs, attn, attn_ptr, row_sim, row_ptr
+        self.score, self.cap_len, self.cross_attn = score, cap_len, cross_attn
+        self._ptr_host = None
+
+    def __len__(self):
+        return self.score.shape[0]
+
+    def _ptr(self):
+        if self._ptr_host is None:
+            self._ptr_host = self.attn_ptr.cpu().numpy()
+        return self._ptr_host
+
+    def matrix(self, p):
+        """the [W, R] attention matrix of pair p (a view): word-major, t2i rows / i2t columns sum to 1"""
+        p = int(p)
+        if not 0 <= p < len(self):
+            raise IndexError("pair %d of %d" % (p, len(self)))
+        ptr = self._ptr()
+        return self.attn[int(ptr[p]):int(ptr[p + 1])].view(-1, SCAN_R)
+
+    def sims(self, p):
+        """the cosine similarities pair p's score is aggregated from: one per word (t2i) or per region (i2t)"""
+        p = int(p)
+        if not 0 <= p < len(self):
+            raise IndexError("pair %d of %d" % (p, len(self)))
+        if self.cross_attn == 'i2t':
+            return self.row_sim[p * SCAN_R:(p + 1) * SCAN_R]
+        ptr = self._ptr()
+        return self.row_sim[int(ptr[p]) // SCAN_R:int(ptr[p + 1]) // SCAN_R]
+
+
+def _attn_lens(plan, dev):
+    """Device copy of ALL captions' true lengths (`_pairs_state` zeroes those the score kernel does not take).  Cached on the plan."""
+    st = getattr(plan, "_attn_lens", None)
+    if st is None or st[0] != dev:
+        st = (dev, h2d(np.asarray(plan.len_host, dtype=np.int32), dev))
+        plan._attn_lens = st
+    return st[1]
+
+
+def scan_pair_attention(images, words, plan, pairs, cross_attn='t2i', raw_feature_norm='clipped_l2norm', agg_func='LogSumExp',
+                        lambda_lse=6.0, lambda_softmax=9.0, workspace=None):
+    """The attention matrices SCAN's scores are aggregated from (func_attention's second result, Objectives.py:421-476; its
+    callers xattn_score_t2i / _i2t :350 / :398), the per-word / per-region cosines and the scores of LISTED pairs:
+    pairs int32 [P, 2] of (image, caption), in any order, duplicates allowed -> ScanPairAttention (csrc/scan_attn.hip).  Every
+    pair's outputs are the same bits whatever else is listed.  Captions of 1..96 words, 36 regions.  Argument checks and
+    `workspace` (scan_pairs_prepare's) as scan_candidate_scores."""
+    lib = _lib.load()
+    if cross_attn not in ('t2i', 'i2t'):
+        raise ValueError("unknown first norm type:", raw_feature_norm)
+    if raw_feature_norm not in _NORMS:
+        raise ValueError("unknown first norm type:", raw_feature_norm)
+    if agg_func not in _AGGS:
+        raise ValueError("unknown aggfunc: {}".format(agg_func))
+    images = _dev(images, name="images")
+    words = _dev(words, name="words")
+    pairs = _dev(pairs, torch.int32, name="pairs")
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError("scan_pair_attention: pairs must be [P, 2] of (image, caption), got shape %s" % (tuple(pairs.shape),))
+    Ni, R, D = images.shape
+    Nc = plan.Nc
+    dev = images.device
+    P = pairs.shape[0]
+    mode = 0 if cross_attn == 't2i' else 1
+    if workspace is not None:
+        if not isinstance(workspace, ScanPairsWorkspace):
+            raise TypeError("scan_pair_attention: workspace must come from scan_pairs_prepare")
+        workspace.check(cross_attn, images, words, plan)
+    if P == 0:
+        z64 = torch.zeros(1, device=dev, dtype=torch.int64)
+        f = lambda: torch.empty(0, device=dev, dtype=torch.float32)
+        return ScanPairAttention(pairs, f(), z64, f(), z64.clone(), f(), torch.empty(0, device=dev, dtype=torch.int32), cross_attn)
+    if R != SCAN_R:
+        raise NotImplementedError("scan_pair_attention: %d regions per image (the pair kernel is built for %d)" % (R, SCAN_R))
+    if len(plan.len_host) and int(plan.len_host.max()) > SCAN_PAIR_MAXW:
+        raise NotImplementedError("scan_pair_attention: captions of %d words (supported: <= %d)" % (int(plan.len_host.max()), SCAN_PAIR_MAXW))
+    if P * SCAN_PAIR_MAXW * SCAN_R >= 2 ** 31:
+        raise NotImplementedError("scan_pair_attention: %d pairs; split the list" % P)
+    lo, hi = torch.aminmax(pairs, dim=0)                          # one device reduction: nothing out of range reaches the kernel
+    (ilo, clo), (ihi, chi) = lo.tolist(), hi.tolist()
+    if ilo < 0 or ihi >= Ni or clo < 0 or chi >= Nc:
+        raise ValueError("scan_pair_attention: pair index out of range: images [%d, %d] of %d, captions [%d, %d] of %d"
+                         % (ilo, ihi, Ni, clo, chi, Nc))
+    lens = _attn_lens(plan, dev)
+    off, _ = _pairs_state(plan, dev)
+    pair_img, pair_cap = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+    cap_len = lens[pair_cap.long()]
+    row_ptr = torch.zeros(P + 1, device=dev, dtype=torch.int64)
+    row_ptr[1:] = torch.cumsum(cap_len, 0, dtype=torch.int64)
+    attn_ptr = row_ptr * SCAN_R
+    n_words = int(row_ptr[-1])
+    attn = torch.empty(n_words * SCAN_R, device=dev, dtype=torch.float32)
+    row_sim = torch.empty(n_words if mode == 0 else P * SCAN_R, device=dev, dtype=torch.float32)
+    score = torch.empty(P, device=dev, dtype=torch.float32)
+    ws = (workspace if workspace is not None else scan_pairs_prepare(images, words, plan, cross_attn)).buf
+    _lib.check(lib.itr_scan_pair_attention(
+        _p(images), _p(words), _p(off), _p(lens), _p(pair_img), _p(pair_cap), P, Ni, Nc, words.shape[0], R, D, mode,
+        _NORMS[raw_feature_norm], _AGGS[agg_func], float(lambda_softmax), float(lambda_lse), _p(attn), _p(attn_ptr), attn.numel(),
+        _p(row_sim), _p(row_ptr), row_sim.numel(), _p(score), _p(ws), ws.numel(), _stream()))
+    return ScanPairAttention(pairs, attn, attn_ptr, row_sim, row_ptr, score, cap_len, cross_attn)
+
+
+def scan_candidate_attention(images, words, plan, cand, by, m=None, **kw):
+    """`scan_pair_attention` for candidate lists, `cand` and `by` as in scan_candidate_scores: explains the first `m` columns of
+    every list (all of them when m is None) -> ScanPairAttention whose pair q * m + k is list q's entry k."""
+    if by not in ('caption', 'image'):
+        raise ValueError("scan_candidate_attention: by must be 'caption' or 'image', got %r" % (by,))
+    cand = _dev(cand, torch.int32, name="cand")
+    if cand.dim() != 2:
+        raise ValueError("scan_candidate_attention: cand must be 2-D, got shape %s" % (tuple(cand.shape),))
+    n_q = plan.Nc if by == 'caption' else images.shape[0]
+    if cand.shape[0] != n_q:
+        raise ValueError("scan_candidate_attention: by=%r needs %d lists, got %d" % (by, n_q, cand.shape[0]))
+    m = cand.shape[1] if m is None else int(m)
+    if m < 0 or m > cand.shape[1]:
+        raise ValueError("scan_candidate_attention: m = %d outside [0, %d]" % (m, cand.shape[1]))
+    flat = cand[:, :m].reshape(-1)
+    qid = torch.arange(n_q, device=cand.device, dtype=torch.int32).repeat_interleave(m)
+    pairs = torch.stack((flat, qid) if by == 'caption' else (qid, flat), 1)
+    return scan_pair_attention(images, words, plan, pairs, **kw)
+
+
 # ------------------------------------------------------------------------------------------ SGRAF on candidate lists
 def _sgraf_pairs_lens(plan, dev):
     """Device copies of ALL captions' offsets and lengths for the SGRAF pair kernels; captions of more than SGRAF_MAX_WORDS words get

@@ -36,7 +36,7 @@ typedef void *itr_stream_t;
 
 const char *itr_last_error(void);
 /* ABI version, bumped on any signature change. */
-#define ITR_ABI_VERSION 34
+#define ITR_ABI_VERSION 35
 int itr_abi_version(void);
 
 /* ---- a1: l2norm / l1norm  (itr/modalmodule/utils.py:4-15) ----------------------------
@@ -418,6 +418,30 @@ int itr_scan_pair_scores(const float *img, const float *words, const int64_t *ca
                          int64_t Nc, int64_t n_rows, int R, int D, int mode, int norm, int agg, float lambda_softmax,
                          float lambda_lse, float *out, int64_t out_len, void *workspace, size_t workspace_bytes,
                          itr_stream_t stream);
+/* ---- a6, explained: the attention matrix func_attention returns next to the weighted context (Objectives.py:421-476, attnT at
+ * :466 / :476; received by xattn_score_t2i :350 and xattn_score_i2t :398), the cosine similarities the score is aggregated from
+ * (:354 / :400, cosine_similarity :10-15) and the score, for P LISTED (image, caption) pairs in any order (csrc/scan_attn.hip) ----
+ * Pair p is (image pair_img[p], caption pair_cap[p]); operands, mode / norm / agg codes and lambdas as itr_scan_pair_scores, and
+ * the workspace is the one itr_scan_pairs_prepare filled for the same mode, used unchanged (read only).
+ *   attn:    the matrix after the first normalisation and Softmax(attn * lambda_softmax), always one [W_c, 36] row-major block
+ *            per pair (word-major) at attn[attn_ptr[p]]; t2i: every word row sums to 1, i2t: every region column sums to 1.
+ *   row_sim: t2i W_c floats at row_sim[row_ptr[p]] (one per word), i2t 36 floats at row_sim[p * 36] (one per region).
+ *   score:   score[p], the aggregate of row_sim.
+ *   attn_ptr / row_ptr: int64 [P + 1] device arrays supplied by the caller (prefix sums of W_c * 36 and of W_c over the list);
+ *   attn_len / row_len: floats the two buffers hold.
+ * cap_len[c] holds the TRUE length, 1..96 (unlike itr_scan_pair_scores).  In mode 1 the prepared workspace holds Gram matrices for
+ * captions of up to 64 words only -- itr_scan_pairs_prepare must have been given length 0 for longer ones, as for the scores --
+ * and this entry computes what it needs for 65..96 words itself.
+ * R != 36, D % 16 != 0 or P * 96 * 36 >= 2^31: ITR_ERR_UNSUPPORTED.  A null pointer, a negative size, an unknown code or a short
+ * workspace: ITR_ERR_BADARG.  What only the device can see is checked there before any dependent load or store: an image or
+ * caption index out of range, a length outside 1..96, word rows outside [0, n_rows) or an output block outside its buffer give
+ * score[p] = NaN and nothing else of that pair is read or written.  A pair's outputs depend on that pair alone: the same bits in
+ * any list, order or blocking.  No atomics. */
+int itr_scan_pair_attention(const float *img, const float *words, const int64_t *cap_off, const int32_t *cap_len,
+                            const int32_t *pair_img, const int32_t *pair_cap, int64_t P, int64_t Ni, int64_t Nc, int64_t n_rows,
+                            int R, int D, int mode, int norm, int agg, float lambda_softmax, float lambda_lse, float *attn,
+                            const int64_t *attn_ptr, int64_t attn_len, float *row_sim, const int64_t *row_ptr, int64_t row_len,
+                            float *score, void *workspace, size_t workspace_bytes, itr_stream_t stream);
 /* ---- a7 on candidate lists: EncoderSimilarity.forward (Fusionmodule.py:406-451, with VisualSA :491-507, TextSA :543-559,
  * SCAN_attention :632-664, AttentionFiltration :615-619, GraphReasoning :581-587) for LISTED (image, caption) pairs ----
  * Only the listed pairs are scored (csrc/sgraf_pairs.hip); no (Ni, Nc) intermediate exists.  A pair's score depends on that pair
