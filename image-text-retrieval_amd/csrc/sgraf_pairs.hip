@@ -28,17 +28,10 @@
 // Budgets.  sgraf_pair_attn_kernel: 512 threads (8 pairs), LDS 79,872 B, 126 VGPRs, no scratch: two workgroups per CU by
 // registers and by LDS.  sgraf_loc_items_kernel: as sgraf_loc_kernel (250 VGPRs, 80 KB LDS, two workgroups per CU).  The other kernels
 // are copies / elementwise: <= 26 VGPRs, at most 4 KB of LDS.
-#include "scan_common.h"
-#include "itr_internal.h"
+#include "sgraf_pairs.h"
 #include "pair_mainloop.h"
 
 namespace itr {
-
-constexpr int GP_PAIRS = 8;                // pairs (= waves) per workgroup of the attention kernel
-constexpr int GP_THREADS = GP_PAIRS * 64;
-constexpr int GP_MAXW = 63;                // words per caption: 63 + the global node = 64 graph nodes
-constexpr int GP_ITEM = SC_NT;             // 64 columns / node rows per item
-constexpr int GP_MAXCAP = 16;              // captions per item
 
 // ---------------------------------------------------------------------------------------------------------------- plan
 // pass 0: items of image i (count); pass 1: the records.  One thread per image walks its pairs in list order (greedy: a caption opens a new
@@ -268,11 +261,7 @@ __global__ __launch_bounds__(256) void sgraf_pair_scatter_kernel(const float *__
 }
 
 // ---------------------------------------------------------------------------------------------------------------- workspaces
-struct GpState {
-    float *img_glo, *cap_glo, *gram, *Wfold[8], *vfold[8];
-    void *packed;
-    size_t bytes;
-};
+// (GpState, GpChunk and the shape check: sgraf_pairs.h)
 // scratch of itr_sgraf_pairs_prepare (the global nodes' intermediates): a buffer of its own, free after the call
 struct GpScratch {
     float *img_ave, *g_emb_v, *l_emb_v, *l_emb_t, *cap_ave, *g_emb_t, *WqT, *WkT;
@@ -287,63 +276,48 @@ static GpScratch gp_scratch(void *base, int64_t Ni, int64_t Nc, int64_t n_rows, 
     t.bytes = c.bytes;
     return t;
 }
-static bool gp_fused(int module, int S) { return module == 1 && S == 256; }
-static GpState gp_state(void *base, int64_t Ni, int64_t Nc, int64_t n_rows, int D, int S, int module, int sgr_step) {
-    WsCarver c(base);
-    GpState t{};
-    t.img_glo = c.take<float>((size_t)Ni * D * 4), t.cap_glo = c.take<float>((size_t)Nc * D * 4);
-    t.gram = c.take<float>((size_t)Ni * SC_R * SC_R * 4);
-    if (module == 1) {
-        for (int k = 0; k < 8; ++k) t.Wfold[k] = c.take<float>((size_t)S * S * 4), t.vfold[k] = c.take<float>((size_t)S * 4);
-        if (gp_fused(module, S)) t.packed = c.take(sgr_fused_weights_bytes(sgr_step > 0 ? sgr_step : 1));
-    }
-    t.bytes = c.bytes;
-    return t;
-}
 
-struct GpChunk {
-    float *wt, *P, *cn, *Xloc, *Aloc, *Aglo, *Xglo, *Yglo, *Qloc, *Yloc, *Qglo, *sc;
-    int64_t *col_src;
-    int32_t *cap_col, *grp_begin, *grp_order;
-    void *fused_ws;
-    int *fused_bad;
-    size_t bytes;
-};
-static GpChunk gp_chunk(void *base, int64_t n_pairs, int64_t n_items, int D, int S, int module, int sgr_step) {
+// ---------------------------------------------------------------------------------------------------------------- stages (a)-(c) of a chunk
+// shared with itr_sgraf_pair_attention (sgraf_attn.hip): both entries reach the node rows through these launches
+int sgraf_pairs_nodes(const float *img, const float *words, const int64_t *cap_off, const int32_t *pair_img, const int32_t *pair_capok,
+                      const int32_t *pair_len, const int32_t *pair_col, const int32_t *item_begin, const int32_t *item_img, int64_t p0,
+                      int64_t n_pairs, int64_t it0, int64_t n_items, int64_t Ni, int64_t n_rows, int D, int S, const itr_sgraf_weights *w,
+                      const GpState &s, const GpChunk &k, hipStream_t st) {
+    int rc;
     const int64_t ncols = n_items * GP_ITEM;
-    WsCarver c(base);
-    GpChunk t{};
-    t.wt = c.take<float>((size_t)ncols * D * 4);
-    t.P = c.take<float>((size_t)ncols * SC_R * 4), t.cn = c.take<float>((size_t)ncols * 4);
-    t.Xloc = c.take<float>((size_t)ncols * S * 4);
-    if (S != 256) t.Aloc = c.take<float>((size_t)ncols * D * 4);
-    t.Aglo = c.take<float>((size_t)n_pairs * D * 4);
-    t.Xglo = c.take<float>((size_t)n_pairs * S * 4);
-    if (module == 1) {
-        t.Yglo = c.take<float>((size_t)n_pairs * S * 4);
-        if (!gp_fused(module, S)) {
-            t.Qloc = c.take<float>((size_t)ncols * S * 4), t.Yloc = c.take<float>((size_t)ncols * S * 4), t.Qglo = c.take<float>((size_t)n_pairs * S * 4);
-        } else {
-            t.fused_ws = c.take(sgr_fused_workspace_bytes(n_items, n_pairs, 0));      // (0: group records only, the packed weights live in the state)
-            t.fused_bad = c.take<int>(256);
-        }
+    const int32_t *pimg = pair_img + p0, *pcap = pair_capok + p0, *plen = pair_len + p0;
+#define GP_TRY(x) { rc = (x); if (rc != ITR_OK) return rc; }
+    hipLaunchKernelGGL(sgraf_pair_index_kernel, dim3((unsigned)ceil_div(n_pairs + 1, (int64_t)256)), dim3(256), 0, st, pair_col, item_begin, p0, n_pairs,
+                       it0, n_items, k.cap_col, k.grp_order, k.grp_begin);
+    ITR_CHECK_LAUNCH("sgraf pairs index");
+    // columns that no caption owns: zero weights, zero norm, zero word -> a defined node row nobody reads
+    ITR_CHECK_HIP(hipMemsetAsync(k.P, 0, (size_t)ncols * SC_R * 4, st));
+    ITR_CHECK_HIP(hipMemsetAsync(k.cn, 0, (size_t)ncols * 4, st));
+    ITR_CHECK_HIP(hipMemsetAsync(k.col_src, 0xff, (size_t)ncols * 8, st));
+    // (a) attention weights + context norms
+    GP_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(sgraf_pair_attn_kernel), sizeof(AttnSmem)));
+    AttnArgs a{img, words, s.gram, cap_off, pimg, pcap, plen, k.cap_col, k.P, k.cn, n_pairs, Ni, ncols, D};
+    hipLaunchKernelGGL(sgraf_pair_attn_kernel, dim3((unsigned)ceil_div(n_pairs, (int64_t)GP_PAIRS)), dim3(GP_THREADS), sizeof(AttnSmem), st, a);
+    ITR_CHECK_LAUNCH("sgraf pairs attention");
+    // (b) the item-tiled word rows, then the local nodes
+    hipLaunchKernelGGL(sgraf_pair_colsrc_kernel, dim3((unsigned)ceil_div(n_pairs, (int64_t)4)), dim3(256), 0, st, pcap, plen, k.cap_col, cap_off, n_pairs,
+                       ncols, k.col_src);
+    hipLaunchKernelGGL(sgraf_pair_gather_kernel, dim3((unsigned)ceil_div(ncols, (int64_t)4)), dim3(256), 0, st, words, k.col_src, ncols, n_rows, D, k.wt);
+    ITR_CHECK_LAUNCH("sgraf pairs gather");
+    if (S == 256) {
+        GP_TRY(sgraf_loc_items(k.P, k.cn, img, Ni, item_img + it0, k.wt, w->loc_w, w->loc_b, k.Xloc, n_items, D, st));
+    } else {
+        hipLaunchKernelGGL(sgraf_pair_ctx_kernel, dim3((unsigned)ncols), dim3(256), 0, st, k.P, k.cn, img, Ni, item_img + it0, k.wt, D, k.Aloc);
+        ITR_CHECK_LAUNCH("sgraf pairs context");
+        GP_TRY(gemm_nt(k.Aloc, D, w->loc_w, D, w->loc_b, k.Xloc, S, ncols, S, D, 0, st));
+        GP_TRY(norm_rows(k.Xloc, k.Xloc, ncols, S, 1e-8f, 0, 0, st));
     }
-    t.sc = c.take<float>((size_t)n_pairs * 4);
-    t.col_src = c.take<int64_t>((size_t)ncols * 8);
-    t.cap_col = c.take<int32_t>((size_t)n_pairs * 4), t.grp_order = c.take<int32_t>((size_t)n_pairs * 4);
-    t.grp_begin = c.take<int32_t>((size_t)(n_items + 1) * 4);
-    t.bytes = c.bytes;
-    return t;
-}
-
-static int gp_check_shape(const char *who, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D, int S, int module, int sgr_step) {
-    if (module != 0 && module != 1) { set_error("Invalid input of config.module_name in configs.py"); return ITR_ERR_BADARG; }
-    ITR_REQUIRE(Ni >= 0 && Nc >= 0 && n_rows >= 0 && D > 0 && S > 0, "%s: bad shape", who);
-    ITR_REQUIRE(Nc < 0x7fffffffLL && Ni <= 65535, "%s: at most 65535 images and 2^31 - 1 captions per call", who);
-    ITR_UNSUPPORTED(R != SC_R, "%s: VisualSA is built for %d regions (BatchNorm1d(36)), got %d", who, SC_R, R);
-    ITR_UNSUPPORTED(S > 1024 || (D % SC_BK) != 0, "%s: need sim_dim <= 1024 and embed dim %% 32 == 0", who);
-    ITR_UNSUPPORTED(module == 1 && (sgr_step < 1 || sgr_step > 8), "%s: sgr_step must be in [1, 8]", who);
-    ITR_UNSUPPORTED(module == 1 && S % 16 != 0, "%s: SGR needs sim_dim %% 16 == 0", who);
+    // (c) the global node of every pair
+    hipLaunchKernelGGL(sgraf_pair_glo_kernel, dim3((unsigned)n_pairs), dim3(256), 0, st, s.img_glo, s.cap_glo, pimg, pcap, Ni, D, k.Aglo);
+    ITR_CHECK_LAUNCH("sgraf pairs glo");
+    GP_TRY(gemm_nt(k.Aglo, D, w->glo_w, D, w->glo_b, k.Xglo, S, n_pairs, S, D, 0, st));
+    GP_TRY(norm_rows(k.Xglo, k.Xglo, n_pairs, S, 1e-8f, 0, 0, st));
+#undef GP_TRY
     return ITR_OK;
 }
 
@@ -446,38 +420,10 @@ extern "C" int itr_sgraf_pair_scores(const float *img, const float *words, const
     if (n_pairs == 0 || Ni == 0 || Nc == 0) return ITR_OK;
     hipStream_t st = as_stream(stream);
     const int64_t ncols = n_items * GP_ITEM;
-    const int32_t *pimg = pair_img + p0, *pcap = pair_capok + p0, *plen = pair_len + p0;
+    const int32_t *pcap = pair_capok + p0, *plen = pair_len + p0;
 #define GP_TRY(x) { rc = (x); if (rc != ITR_OK) return rc; }
-    hipLaunchKernelGGL(sgraf_pair_index_kernel, dim3((unsigned)ceil_div(n_pairs + 1, (int64_t)256)), dim3(256), 0, st, pair_col, item_begin, p0, n_pairs,
-                       it0, n_items, k.cap_col, k.grp_order, k.grp_begin);
-    ITR_CHECK_LAUNCH("sgraf pairs index");
-    // columns that no caption owns: zero weights, zero norm, zero word -> a defined node row nobody reads
-    ITR_CHECK_HIP(hipMemsetAsync(k.P, 0, (size_t)ncols * SC_R * 4, st));
-    ITR_CHECK_HIP(hipMemsetAsync(k.cn, 0, (size_t)ncols * 4, st));
-    ITR_CHECK_HIP(hipMemsetAsync(k.col_src, 0xff, (size_t)ncols * 8, st));
-    // (a) attention weights + context norms
-    GP_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(sgraf_pair_attn_kernel), sizeof(AttnSmem)));
-    AttnArgs a{img, words, s.gram, cap_off, pimg, pcap, plen, k.cap_col, k.P, k.cn, n_pairs, Ni, ncols, D};
-    hipLaunchKernelGGL(sgraf_pair_attn_kernel, dim3((unsigned)ceil_div(n_pairs, (int64_t)GP_PAIRS)), dim3(GP_THREADS), sizeof(AttnSmem), st, a);
-    ITR_CHECK_LAUNCH("sgraf pairs attention");
-    // (b) the item-tiled word rows, then the local nodes
-    hipLaunchKernelGGL(sgraf_pair_colsrc_kernel, dim3((unsigned)ceil_div(n_pairs, (int64_t)4)), dim3(256), 0, st, pcap, plen, k.cap_col, cap_off, n_pairs,
-                       ncols, k.col_src);
-    hipLaunchKernelGGL(sgraf_pair_gather_kernel, dim3((unsigned)ceil_div(ncols, (int64_t)4)), dim3(256), 0, st, words, k.col_src, ncols, n_rows, D, k.wt);
-    ITR_CHECK_LAUNCH("sgraf pairs gather");
-    if (S == 256) {
-        GP_TRY(sgraf_loc_items(k.P, k.cn, img, Ni, item_img + it0, k.wt, w->loc_w, w->loc_b, k.Xloc, n_items, D, st));
-    } else {
-        hipLaunchKernelGGL(sgraf_pair_ctx_kernel, dim3((unsigned)ncols), dim3(256), 0, st, k.P, k.cn, img, Ni, item_img + it0, k.wt, D, k.Aloc);
-        ITR_CHECK_LAUNCH("sgraf pairs context");
-        GP_TRY(gemm_nt(k.Aloc, D, w->loc_w, D, w->loc_b, k.Xloc, S, ncols, S, D, 0, st));
-        GP_TRY(norm_rows(k.Xloc, k.Xloc, ncols, S, 1e-8f, 0, 0, st));
-    }
-    // (c) the global node of every pair
-    hipLaunchKernelGGL(sgraf_pair_glo_kernel, dim3((unsigned)n_pairs), dim3(256), 0, st, s.img_glo, s.cap_glo, pimg, pcap, Ni, D, k.Aglo);
-    ITR_CHECK_LAUNCH("sgraf pairs glo");
-    GP_TRY(gemm_nt(k.Aglo, D, w->glo_w, D, w->glo_b, k.Xglo, S, n_pairs, S, D, 0, st));
-    GP_TRY(norm_rows(k.Xglo, k.Xglo, n_pairs, S, 1e-8f, 0, 0, st));
+    GP_TRY(sgraf_pairs_nodes(img, words, cap_off, pair_img, pair_capok, pair_len, pair_col, item_begin, item_img, p0, n_pairs, it0, n_items, Ni, n_rows,
+                             D, S, w, s, k, st));
     // SAF / SGR on the chunk as one virtual image row: caption j = pair p0 + j
     const bool fused = gp_fused(module, S);
     if (module == 1) ITR_CHECK_HIP(hipMemsetAsync(k.Yglo, 0, (size_t)n_pairs * S * 4, st));

@@ -119,6 +119,9 @@ SIGNATURES = {
     "itr_sgraf_pair_scores_workspace_bytes": (sz, [i64, i64, i32, i32, i32, i32]),
     "itr_sgraf_pair_scores": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, sz,
                                     vp, i64, vp, sz, vp]),
+    "itr_sgraf_pair_attention_workspace_bytes": (sz, [i64, i64, i32, i32, i32, i32]),
+    "itr_sgraf_pair_attention": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, sz,
+                                       vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, sz, vp]),
     "itr_scan_pair_scores": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, f32, f32, vp, i64, vp, sz, vp]),
     "itr_scan_pair_attention": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, i64, vp, vp, i64,
                                       vp, vp, sz, vp]),

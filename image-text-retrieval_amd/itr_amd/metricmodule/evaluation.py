@@ -456,7 +456,7 @@ def explain(lists, score_fn, m):
     [n m + 1], d_cap_len int32 [n m].  With the data layer's `boxes`, region r of d_attn's column r is the box to draw."""
     attention = getattr(score_fn, 'attention', None)
     if attention is None:
-        raise NotImplementedError("explain: attention maps exist for a SCAN fine model only")
+        raise NotImplementedError("explain: attention maps exist for a SCAN fine model only (an SGRAF scorer explains itself through explain_sgraf)")
     m = int(m)
     out = {}
     for d, by in (('i2t', 'image'), ('t2i', 'caption')):
@@ -477,6 +477,40 @@ def explain(lists, score_fn, m):
 _explain_lists = explain          # evalrank_rerank's keyword `explain` hides the function there
 
 
+def explain_sgraf(lists, score_fn, m):
+    """Why an SGRAF fine model preferred a result: for the best `m` results of every query in both directions, the word-by-region
+    attention, SAF's filtration weights over the alignment nodes or SGR's graph edges at every step, and the score.
+    lists: `rerank`'s (reranked) lists; score_fn: `_sgraf_score_fn`'s (it carries `reasoning`); 1 <= m <= k.
+    -> dict of host arrays, per direction d in ('i2t', 't2i'): d_idx int64 [n, m], d_scores float32 [n, m], d_attn float32 (flat;
+    pair q * m + j holds its [W, 36] word-major block at d_attn_ptr), d_attn_ptr int64 [n m + 1], then for SAF d_node_w /
+    d_node_ptr (W + 1 weights per pair, node 0 = the global node) or for SGR d_edge / d_edge_ptr ([sgr_step, W + 1, W + 1] per
+    pair), d_cap_len int32 [n m] and d_explained bool [n m] (False: a caption of more than 63 words, scored but with empty blocks)."""
+    reasoning = getattr(score_fn, 'reasoning', None)
+    if reasoning is None:
+        raise NotImplementedError("explain_sgraf: reasoning maps exist for an SGRAF fine model only (SCAN: explain)")
+    m = int(m)
+    out = {}
+    for d, by in (('i2t', 'image'), ('t2i', 'caption')):
+        idx = np.asarray(lists[d + '_topk'])
+        if m < 1 or m > idx.shape[1]:
+            raise ValueError("explain_sgraf: m = %d outside [1, %d]" % (m, idx.shape[1]))
+        dev = torch.device('cuda', torch.cuda.current_device())
+        cand = torch.from_numpy(np.ascontiguousarray(idx[:, :m]).astype(np.int32)).to(dev)
+        a = reasoning(cand, by, m)
+        n = idx.shape[0]
+        out.update({d + '_idx': idx[:, :m].astype(np.int64), d + '_scores': a.score.cpu().numpy().reshape(n, m),
+                    d + '_attn': a.attn.cpu().numpy(), d + '_attn_ptr': a.attn_ptr.cpu().numpy(),
+                    d + '_cap_len': a.cap_len.cpu().numpy(), d + '_explained': a.explained.cpu().numpy()})
+        if a.node_w is not None:
+            out.update({d + '_node_w': a.node_w.cpu().numpy(), d + '_node_ptr': a.node_ptr.cpu().numpy()})
+        else:
+            out.update({d + '_edge': a.edge.cpu().numpy(), d + '_edge_ptr': a.edge_ptr.cpu().numpy()})
+    return out
+
+
+_explain_sgraf_lists = explain_sgraf
+
+
 def _packed_words(img_embs, cap_embs, cap_lens):
     """encode_data's padded word-level embeddings -> (images, packed words, ScanPlan) on the current device"""
     dev = torch.device('cuda', torch.cuda.current_device())
@@ -492,13 +526,18 @@ def _packed_words(img_embs, cap_embs, cap_lens):
 
 def _sgraf_score_fn(model, img_embs, cap_embs, cap_lens):
     """score_fn of `rerank` for an SGRAF model (SAF or SGR): the captions packed once, the per-image / per-caption state (global
-    vectors, Gram matrices, SGR's folded weights) prepared once and used for both list directions."""
+    vectors, Gram matrices, SGR's folded weights) prepared once and used for both list directions.
+    Its attribute `reasoning(cand, by, m)` is ops.sgraf_candidate_attention on the same operands and state (`explain_sgraf`)."""
     images, words, plan = _packed_words(img_embs, cap_embs, cap_lens)
     enc = model.sim_enc
     weights = {k_: v.detach() for k_, v in enc.state_dict().items()}
     state = ops.sgraf_pairs_prepare(images, words, plan, weights, enc.module_name, enc.sgr_step)
-    return lambda cand, by: ops.sgraf_candidate_scores(images, words, plan, weights, cand, by, module_name=enc.module_name,
-                                                       sgr_step=enc.sgr_step, state=state)
+    kw = dict(module_name=enc.module_name, sgr_step=enc.sgr_step, state=state)
+
+    def fn(cand, by):
+        return ops.sgraf_candidate_scores(images, words, plan, weights, cand, by, **kw)
+    fn.reasoning = lambda cand, by, m: ops.sgraf_candidate_attention(images, words, plan, weights, cand, by, m=m, **kw)
+    return fn
 
 
 def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
@@ -524,13 +563,14 @@ def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
     return fn
 
 
-def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split='dev', fold5=False, explain=None):
+def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split='dev', fold5=False, explain=None, explain_sgraf=None):
     """Coarse-to-fine evaluation: the coarse model (any family evalrank_single scores) shortlists k candidates per query in both
     directions, the fine model -- SCAN (either cross_attn) or SGRAF (SAF or SGR) -- scores only those pairs, Recall@K is that of the reranked ranking
     (`rerank`).  Writes `<data_name>[_5fold]_rerank<k>_result.yaml` (the coarse-only numbers under 'coarse', the reranked ones
     under 'rerank') and the reranked lists `<data_name>[_5fold]_rerank<k>.npz` next to the coarse checkpoint.
     explain=M (1 <= M <= k, SCAN fine model, not with fold5): after re-ordering, the best M results of every query in both
-    directions are explained (`explain`) and written to `<data_name>_rerank<k>_explain<M>.npz` next to the other files."""
+    directions are explained (`explain`) and written to `<data_name>_rerank<k>_explain<M>.npz` next to the other files.
+    explain_sgraf=M (the same rules, SGRAF fine model): `explain_sgraf`'s arrays go to `<data_name>_rerank<k>_explain<M>_sgraf.npz`."""
     import os
     import yaml
     from ..datamodule import data_loader as data
@@ -542,13 +582,23 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
             raise ValueError("evalrank_rerank: explain does not combine with fold5")
         if explain_m < 1 or explain_m > int(k):
             raise ValueError("evalrank_rerank: explain = %d outside [1, k = %d]" % (explain_m, int(k)))
+    sgraf_m = None if explain_sgraf is None else int(explain_sgraf)
+    if sgraf_m is not None:
+        if fold5:
+            raise ValueError("evalrank_rerank: explain_sgraf does not combine with fold5")
+        if sgraf_m < 1 or sgraf_m > int(k):
+            raise ValueError("evalrank_rerank: explain_sgraf = %d outside [1, k = %d]" % (sgraf_m, int(k)))
     coarse, c_cfg = _load_for_eval(model_path_coarse, data_path)
     fine, f_cfg = _load_for_eval(model_path_fine, data_path)
     if f_cfg['name'] not in ('SCAN', 'SGRAF'):
         raise NotImplementedError("evalrank_rerank: the fine model must be SCAN or SGRAF (candidate-list scoring exists for these only), got %s"
                                   % f_cfg['name'])
     if explain_m is not None and f_cfg['name'] != 'SCAN':
-        raise NotImplementedError("evalrank_rerank: explain needs a SCAN fine model (attention maps exist for SCAN only), got %s" % f_cfg['name'])
+        raise NotImplementedError("evalrank_rerank: explain needs a SCAN fine model (attention maps exist for SCAN only; an SGRAF model "
+                                  "explains itself through explain_sgraf), got %s" % f_cfg['name'])
+    if sgraf_m is not None and f_cfg['name'] != 'SGRAF':
+        raise NotImplementedError("evalrank_rerank: explain_sgraf needs an SGRAF fine model (a SCAN model explains itself through explain), got %s"
+                                  % f_cfg['name'])
     fine_score_fn = _scan_score_fn if f_cfg['name'] == 'SCAN' else _sgraf_score_fn
     if f_cfg['data_name'] != c_cfg['data_name']:
         raise ValueError("evalrank_rerank: the checkpoints name different datasets (%s, %s): their lists would not index the same items"
@@ -561,7 +611,7 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
     if len(c_img) != len(f_img) or len(c_cap) != len(f_cap):
         raise ValueError("evalrank_rerank: the two models' loaders hold different item counts (%d / %d images, %d / %d captions)"
                          % (len(c_img), len(f_img), len(c_cap), len(f_cap)))
-    lists, explained = {}, {}
+    lists, explained, reasoned = {}, {}, {}
 
     def block(sl_img, sl_cap, prefix):
         sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
@@ -571,6 +621,8 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
         lists.update({prefix + key: v for key, v in tl.items()})
         if explain_m is not None:
             explained.update(_explain_lists(tl, fn, explain_m))
+        if sgraf_m is not None:
+            reasoned.update(_explain_sgraf_lists(tl, fn, sgraf_m))
         res_r = _recall_dict((i_ranks, tl['i2t_topk'][:, 0], t_ranks, tl['t2i_topk'][:, 0]))
         print("Reranked (k = %d) image to text: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((k,) + tuple(r)))
         print("Reranked (k = %d) text to image: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((k,) + tuple(ri)))
@@ -598,4 +650,6 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
     np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}.npz'), **lists)
     if explain_m is not None:
         np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_explain{explain_m}.npz'), **explained)
+    if sgraf_m is not None:
+        np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_explain{sgraf_m}_sgraf.npz'), **reasoned)
     return res_dic

@@ -1572,6 +1572,212 @@ def sgraf_candidate_scores(images, words, plan, weights, cand, by, module_name='
     return out
 
 
+# ------------------------------------------------------------------------------------------ SGRAF reasoning maps of listed pairs
+SGRAF_ATTN_MAX_SIM_DIM = 256   # csrc/sgraf_attn.hip keeps an item's node rows on chip
+
+
+class SgrafPairAttention:
+    """What `sgraf_pair_attention` returns for P pairs, all on the device, in the caller's order.  Pair p has W_p words and
+    n_p = W_p + 1 alignment nodes; NODE 0 IS THE GLOBAL NODE, node 1 + w is word w.
+      attn / attn_ptr     float32 flat / int64 [P + 1]: the [W_p, 36] row-major SCAN_attention weights (rows sum to 1)
+      node_w / node_ptr   SAF only: AttentionFiltration's n_p weights (sum to 1); None for SGR
+      edge / edge_ptr     SGR only: GraphReasoning's [sgr_step, n_p, n_p] edges (rows sum to 1); None for SAF
+      score float32 [P], cap_len int32 [P] (W_p), explained bool [P], pairs int32 [P, 2].
+    A caption of more than 63 words has its score and explained[p] False: its blocks have length 0."""
+
+    def __init__(self, pairs, attn, attn_ptr, node_w, node_ptr, edge, edge_ptr, score, cap_len, explained, module_name, sgr_step):
+        self.pairs, self.attn, self.attn_ptr, self.node_w, self.node_ptr = pairs, attn, attn_ptr, node_w, node_ptr
+        self.edge, self.edge_ptr, self.score, self.cap_len, self.explained = edge, edge_ptr, score, cap_len, explained
+        self.module_name, self.sgr_step = module_name, int(sgr_step)
+        self._host = {}
+
+    def __len__(self):
+        return self.score.shape[0]
+
+    def _span(self, name, p):
+        p = int(p)
+        if not 0 <= p < len(self):
+            raise IndexError("pair %d of %d" % (p, len(self)))
+        if name not in self._host:
+            self._host[name] = getattr(self, name).cpu().numpy()
+        ptr = self._host[name]
+        return int(ptr[p]), int(ptr[p + 1])
+
+    def matrix(self, p):
+        """the [W, 36] word x region attention of pair p (a view); [0, 36] for a pair that is not explained"""
+        b, e = self._span('attn_ptr', p)
+        return self.attn[b:e].view(-1, SCAN_R)
+
+    def nodes(self, p):
+        """SAF: the filtration weights of pair p's W + 1 nodes (a view), the global node first"""
+        if self.node_w is None:
+            raise ValueError("nodes: filtration weights exist for module SAF, this is %s" % self.module_name)
+        b, e = self._span('node_ptr', p)
+        return self.node_w[b:e]
+
+    def edges(self, p):
+        """SGR: the [sgr_step, W + 1, W + 1] graph edges of pair p (a view), row = querying node"""
+        if self.edge is None:
+            raise ValueError("edges: graph edges exist for module SGR, this is %s" % self.module_name)
+        b, e = self._span('edge_ptr', p)
+        n = int(round(((e - b) / max(self.sgr_step, 1)) ** 0.5))
+        return self.edge[b:e].view(self.sgr_step, n, n)
+
+
+SGRAF_ATTN_LAST = {}           # diagnostics: chunks, items and workspace of the last sgraf_pair_attention call
+
+
+def sgraf_pair_attention(images, words, plan, weights, pairs, module_name='SAF', sgr_step=3, state=None, max_workspace_bytes=None):
+    """Why SGRAF scored LISTED pairs as it did: pairs int32 [P, 2] of (image, caption) in any order, duplicates allowed ->
+    SgrafPairAttention with SCAN_attention's word x region weights (Fusionmodule.py:632-664), SAF's filtration weights over the
+    alignment nodes (:615-619) or SGR's graph edges at every step (:581-587), and the scores (:406-451) (csrc/sgraf_attn.hip).
+    The pairs are regrouped image-major on the device as in sgraf_candidate_scores and the results come back in the caller's
+    order; every pair's outputs are the same bits whatever else is listed, in any order, under any workspace budget.  36 regions,
+    D % 32 == 0, sim_dim % 16 == 0 and <= 256 (NotImplementedError above), captions of 1..63 words.  A caption of 64..191 words is
+    SCORED by the path sgraf_candidate_scores uses for it and not explained (empty blocks, explained[p] False); longer captions
+    raise NotImplementedError.  `state` (sgraf_pairs_prepare's) and `max_workspace_bytes` as sgraf_candidate_scores."""
+    lib = _lib.load()
+    if module_name not in ('SAF', 'SGR'):
+        raise ValueError('Invalid input of config.module_name in configs.py')
+    images = _dev(images, name="images")
+    words = _dev(words, name="words")
+    pairs = _dev(pairs, torch.int32, name="pairs")
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError("sgraf_pair_attention: pairs must be [P, 2] of (image, caption), got shape %s" % (tuple(pairs.shape),))
+    Ni, R, D = images.shape
+    Nc = plan.Nc
+    dev = images.device
+    P = pairs.shape[0]
+    sgr = module_name == 'SGR'
+    steps = int(sgr_step) if sgr else 0
+    if state is not None:
+        if not isinstance(state, SgrafPairsState):
+            raise TypeError("sgraf_pair_attention: state must come from sgraf_pairs_prepare")
+        state.check(images, words, plan, weights, module_name, sgr_step)
+    S_dim = int(weights["sim_eval_w.weight"].shape[-1])
+    if S_dim > SGRAF_ATTN_MAX_SIM_DIM or S_dim % 16:
+        raise NotImplementedError("sgraf_pair_attention: sim_dim %d (supported: multiples of 16 up to %d)" % (S_dim, SGRAF_ATTN_MAX_SIM_DIM))
+    f32 = lambda n: torch.empty(n, device=dev, dtype=torch.float32)
+    if P == 0:
+        z = lambda: torch.zeros(1, device=dev, dtype=torch.int64)
+        return SgrafPairAttention(pairs, f32(0), z(), None if sgr else f32(0), None if sgr else z(), f32(0) if sgr else None, z() if sgr else None,
+                                  f32(0), torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.bool),
+                                  module_name, sgr_step)
+    if R != SCAN_R:
+        raise NotImplementedError("sgraf_pair_attention: %d regions per image (VisualSA is built for %d)" % (R, SCAN_R))
+    if len(plan.len_host) and int(plan.len_host.max()) > SGRAF_COMPOSED_MAX_WORDS:
+        raise NotImplementedError("sgraf_pair_attention: captions of at most %d words are supported" % SGRAF_COMPOSED_MAX_WORDS)
+    if P >= 2 ** 31 // 64:
+        raise NotImplementedError("sgraf_pair_attention: %d pairs (at most %d per call); split the list" % (P, 2 ** 31 // 64 - 1))
+    lo, hi = torch.aminmax(pairs, dim=0)                          # one device reduction: nothing out of range reaches the kernels
+    (ilo, clo), (ihi, chi) = lo.tolist(), hi.tolist()
+    if ilo < 0 or ihi >= Ni or clo < 0 or chi >= Nc:
+        raise ValueError("sgraf_pair_attention: pair index out of range: images [%d, %d] of %d, captions [%d, %d] of %d"
+                         % (ilo, ihi, Ni, clo, chi, Nc))
+    if state is None:
+        state = sgraf_pairs_prepare(images, words, plan, weights, module_name, sgr_step)
+    st = state.struct
+    mod = 1 if sgr else 0
+    # ---- the output layout, on the device
+    imgs, caps = pairs[:, 0].to(torch.int64), pairs[:, 1].to(torch.int64)
+    cap_len = _attn_lens(plan, dev)[caps]
+    explained = cap_len <= SGRAF_MAX_WORDS
+    w_eff = torch.where(explained, cap_len, torch.zeros_like(cap_len)).to(torch.int64)
+    n_eff = torch.where(explained, w_eff + 1, torch.zeros_like(w_eff))
+
+    def prefix(counts):
+        ptr = torch.zeros(P + 1, device=dev, dtype=torch.int64)
+        ptr[1:] = torch.cumsum(counts, 0)
+        return ptr
+
+    attn_ptr = prefix(w_eff * SCAN_R)
+    aux_ptr = prefix(n_eff * n_eff * steps if sgr else n_eff)
+    ends = torch.stack((attn_ptr[-1], aux_ptr[-1])).tolist()
+    attn, aux, score = f32(ends[0]), f32(ends[1]), f32(P)
+    result = SgrafPairAttention(pairs, attn, attn_ptr, None if sgr else aux, None if sgr else aux_ptr, aux if sgr else None,
+                                aux_ptr if sgr else None, score, cap_len, explained, module_name, sgr_step)
+    slot = torch.arange(P, device=dev, dtype=torch.int64)
+    if len(plan.len_host) and int(plan.len_host.max()) > SGRAF_MAX_WORDS:
+        lm = ~explained
+        _sgraf_long_caption_pairs(images, words, plan, weights, module_name, sgr_step, S_dim, caps[lm], imgs[lm], slot[lm], score)
+        caps, imgs, slot = caps[~lm], imgs[~lm], slot[~lm]
+    Ps = caps.numel()
+    SGRAF_ATTN_LAST.update(pairs=Ps, items=0, chunks=0, workspace_bytes=0)
+    if Ps == 0:
+        return result
+    # ---- image-major (CSR) form, on the device
+    imgs, order = torch.sort(imgs, stable=True)
+    caps, slot = caps[order], slot[order]
+    img_ptr = torch.zeros(Ni + 1, device=dev, dtype=torch.int32)
+    img_ptr[1:] = torch.cumsum(torch.bincount(imgs, minlength=Ni), 0).to(torch.int32)
+    pair_img, pair_cap, pair_out = imgs.to(torch.int32), caps.to(torch.int32), slot.to(torch.int32)
+    off, klen = _sgraf_pairs_lens(plan, dev)
+    pair_len, pair_col, pair_capok = (torch.empty(Ps, device=dev, dtype=torch.int32) for _ in range(3))
+    item_begin = torch.empty(Ps + 1, device=dev, dtype=torch.int32)
+    item_img = torch.empty(Ps, device=dev, dtype=torch.int32)
+    n_items_dev = torch.zeros(1, device=dev, dtype=torch.int32)
+    pwb = lib.itr_sgraf_pairs_plan_workspace_bytes(Ni)
+    pws = torch.empty(max(pwb, 1), device=dev, dtype=torch.uint8)
+    _lib.check(lib.itr_sgraf_pairs_plan(_p(img_ptr), _p(pair_cap), _p(off), _p(klen), Ps, Ni, Nc, words.shape[0], _p(pair_len), _p(pair_col),
+                                        _p(pair_capok), _p(item_begin), _p(item_img), _p(n_items_dev), _p(pws), pwb, _stream()))
+    n_items = int(n_items_dev)
+    ib = item_begin[:n_items + 1].cpu().numpy().astype(np.int64)
+    # ---- chunks of whole items sized to the budget
+    if max_workspace_bytes is None:
+        free, _total = torch.cuda.mem_get_info(dev)
+        cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        budget = int(0.9 * (free + cached))
+    else:
+        budget = int(max_workspace_bytes)
+
+    def need(it0, it1):
+        return lib.itr_sgraf_pair_attention_workspace_bytes(int(ib[it1] - ib[it0]), it1 - it0, D, S_dim, mod, int(sgr_step))
+
+    chunks, it0 = [], 0
+    while it0 < n_items:
+        if need(it0, it0 + 1) > budget:
+            raise torch.cuda.OutOfMemoryError("sgraf_pair_attention: one item needs %d bytes of workspace, %d allowed" % (need(it0, it0 + 1), budget))
+        lo_, hi_ = it0 + 1, n_items                             # the largest it1 whose chunk fits (need is monotone)
+        while lo_ < hi_:
+            mid = (lo_ + hi_ + 1) // 2
+            if need(it0, mid) <= budget:
+                lo_ = mid
+            else:
+                hi_ = mid - 1
+        chunks.append((it0, lo_))
+        it0 = lo_
+    wsb = max(need(a, b) for a, b in chunks)
+    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+    SGRAF_ATTN_LAST.update(items=n_items, chunks=len(chunks), workspace_bytes=int(wsb), budget_bytes=budget)
+    node_args = (None, None, 0, _p(aux), _p(aux_ptr), aux.numel()) if sgr else (_p(aux), _p(aux_ptr), aux.numel(), None, None, 0)
+    for a, b in chunks:
+        _lib.check(lib.itr_sgraf_pair_attention(_p(images), _p(words), _p(off), _p(pair_img), _p(pair_capok), _p(pair_len), _p(pair_col),
+                                                _p(pair_out), _p(item_begin), _p(item_img), int(ib[a]), int(ib[b] - ib[a]), a, b - a, Ni, Nc,
+                                                words.shape[0], R, D, S_dim, mod, int(sgr_step), C.byref(st), _p(state.buf), state.buf.numel(),
+                                                _p(attn), _p(attn_ptr), attn.numel(), *node_args, _p(score), P, _p(ws), wsb, _stream()))
+    return result
+
+
+def sgraf_candidate_attention(images, words, plan, weights, cand, by, m=None, **kw):
+    """`sgraf_pair_attention` for candidate lists, `cand` and `by` as in sgraf_candidate_scores: explains the first `m` columns of
+    every list (all of them when m is None) -> SgrafPairAttention whose pair q * m + k is list q's entry k."""
+    if by not in ('caption', 'image'):
+        raise ValueError("sgraf_candidate_attention: by must be 'caption' or 'image', got %r" % (by,))
+    cand = _dev(cand, torch.int32, name="cand")
+    if cand.dim() != 2:
+        raise ValueError("sgraf_candidate_attention: cand must be 2-D, got shape %s" % (tuple(cand.shape),))
+    n_q = plan.Nc if by == 'caption' else images.shape[0]
+    if cand.shape[0] != n_q:
+        raise ValueError("sgraf_candidate_attention: by=%r needs %d lists, got %d" % (by, n_q, cand.shape[0]))
+    m = cand.shape[1] if m is None else int(m)
+    if m < 0 or m > cand.shape[1]:
+        raise ValueError("sgraf_candidate_attention: m = %d outside [0, %d]" % (m, cand.shape[1]))
+    flat = cand[:, :m].reshape(-1)
+    qid = torch.arange(n_q, device=cand.device, dtype=torch.int32).repeat_interleave(m)
+    pairs = torch.stack((flat, qid) if by == 'caption' else (qid, flat), 1)
+    return sgraf_pair_attention(images, words, plan, weights, pairs, **kw)
+
+
 def _sgraf_long_caption_pairs(images, words, plan, weights, module_name, sgr_step, S_dim, caps, imgs, slot, out):
     """Listed pairs of captions with 64..191 words: Fusionmodule.encoder_similarity_train(training=False) -- what sgraf_scores runs for
     such captions -- on each caption's listed images, then a gather into the lists' slots."""

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Evaluate checkpoints like the reference's test.py:  python test.py MODEL_PATH [MODEL_PATH_2] [--data-path P]
-[--split test|testall|dev] [--fold5] [--topk K] [--rerank K [--explain M]]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
+[--split test|testall|dev] [--fold5] [--topk K] [--rerank K [--explain M | --explain-sgraf M]]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
 (and with --topk K the top-K retrieval lists of every query in <data_name>[_5fold]_{single,ensemble}_top<K>.npz).
 python test.py COARSE_PATH FINE_PATH --rerank K: coarse-to-fine retrieval, the first model shortlists K candidates per query and the
 second (SCAN or SGRAF) scores only those  ->  <data_name>[_5fold]_rerank<K>_result.yaml and <data_name>[_5fold]_rerank<K>.npz
 With --explain M (SCAN fine model): also the word-by-region attention maps, per-word / per-region similarities and scores of the
-best M results of every query  ->  <data_name>_rerank<K>_explain<M>.npz"""
+best M results of every query  ->  <data_name>_rerank<K>_explain<M>.npz
+With --explain-sgraf M (SGRAF fine model): the word-by-region attention, SAF's filtration weights or SGR's graph edges of every
+step, and the scores of the best M results of every query  ->  <data_name>_rerank<K>_explain<M>_sgraf.npz"""
 import argparse
 import os
 import sys
@@ -27,16 +29,21 @@ if __name__ == "__main__":
                     help="two checkpoints COARSE FINE: FINE (SCAN or SGRAF) re-scores only COARSE's top-K candidates of every query")
     ap.add_argument("--explain", type=int, default=None, metavar="M",
                     help="with --rerank K and a SCAN fine model: also write the attention maps of the best M <= K results of every query")
+    ap.add_argument("--explain-sgraf", type=int, default=None, metavar="M",
+                    help="with --rerank K and an SGRAF fine model: also write the attention, filtration weights (SAF) or graph edges (SGR) "
+                         "of the best M <= K results of every query")
     a = ap.parse_args()
     if a.explain is not None and not a.rerank:
         ap.error("--explain needs --rerank K")
+    if a.explain_sgraf is not None and not a.rerank:
+        ap.error("--explain-sgraf needs --rerank K")
     if a.rerank:
         if len(a.model_path) != 2:
             ap.error("--rerank needs two checkpoints: COARSE FINE")
         if a.fast or a.topk:
             ap.error("--rerank does not combine with --fast or --topk (the reranked lists are written to ..._rerank<K>.npz)")
         evaluation.evalrank_rerank(a.model_path[0], a.model_path[1], a.rerank, data_path=a.data_path, split=a.split, fold5=a.fold5,
-                                   explain=a.explain)
+                                   explain=a.explain, explain_sgraf=a.explain_sgraf)
     elif a.fast:
         import torch
         import torch.distributed as dist

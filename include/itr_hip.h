@@ -479,6 +479,32 @@ int itr_sgraf_pair_scores(const float *img, const float *words, const int64_t *c
                           int64_t n_items, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D, int S, int module, int sgr_step,
                           const itr_sgraf_weights *w, const void *state, size_t state_bytes, float *out, int64_t out_len,
                           void *workspace, size_t workspace_bytes, itr_stream_t stream);
+/* ---- a7 on candidate lists, explained: what the SGRAF score of a LISTED pair is made of (csrc/sgraf_attn.hip) ----
+ * The word x region attention of SCAN_attention (Fusionmodule.py:632-664), AttentionFiltration's weights over the alignment nodes
+ * (:615-619) or GraphReasoning's edges at every step (:581-587), and the score of EncoderSimilarity.forward (Fusionmodule.py:406-451).
+ * Operands, state (itr_sgraf_pairs_prepare), plan arrays (itr_sgraf_pairs_plan) and the chunk range p0, n_pairs, it0, n_items exactly as
+ * itr_sgraf_pair_scores; the attention, the local and the global node rows are computed by the same kernels on the same bits.
+ * Narrower than the score entry: sim_dim % 16 == 0 and sim_dim <= 256 (ITR_ERR_UNSUPPORTED above: the item's node rows are held on chip).
+ * Pair p of the chunk has W = pair_len[p] words, n = W + 1 nodes -- node 0 is the GLOBAL node, node 1 + w is word w -- and writes to
+ * slot o = pair_out[p] of caller-owned buffers, laid out by caller-owned int64 prefix arrays of out_len + 1 entries:
+ *   attn   [W, 36] row-major at attn[attn_ptr[o]]: the softmax weights of SCAN_attention, every word row sums to 1
+ *   node_w n floats at node_w[node_ptr[o]] (module 0, SAF): l1norm(sigmoid(bn(attn_sim_w x_j))), sums to 1; unused for module 1
+ *   edge   [sgr_step, n, n] at edge[edge_ptr[o]] (module 1, SGR): softmax(q k^T) of every step, every row sums to 1; unused for module 0
+ *   score  score[o]
+ * attn_len / node_len / edge_len: floats the buffers hold; out_len: slots.  Every block is checked against these on the device before the
+ * first dependent access: a pair whose blocks do not fit, or which the plan marked as not scorable, gets score NaN and nothing else of it
+ * is written; a slot outside [0, out_len) is skipped.  A pair's outputs depend on that pair alone (fixed K order, no atomics): the same
+ * bits in any list, order, item or chunk.  workspace: itr_sgraf_pair_attention_workspace_bytes, monotone in both counts.
+ * ITR_ABI_VERSION stays 35: these two entries are purely additive, no existing signature changed. */
+size_t itr_sgraf_pair_attention_workspace_bytes(int64_t n_pairs, int64_t n_items, int D, int S, int module, int sgr_step);
+int itr_sgraf_pair_attention(const float *img, const float *words, const int64_t *cap_off, const int32_t *pair_img,
+                             const int32_t *pair_capok, const int32_t *pair_len, const int32_t *pair_col, const int32_t *pair_out,
+                             const int32_t *item_begin, const int32_t *item_img, int64_t p0, int64_t n_pairs, int64_t it0,
+                             int64_t n_items, int64_t Ni, int64_t Nc, int64_t n_rows, int R, int D, int S, int module, int sgr_step,
+                             const itr_sgraf_weights *w, const void *state, size_t state_bytes, float *attn, const int64_t *attn_ptr,
+                             int64_t attn_len, float *node_w, const int64_t *node_ptr, int64_t node_len, float *edge,
+                             const int64_t *edge_ptr, int64_t edge_len, float *score, int64_t out_len, void *workspace,
+                             size_t workspace_bytes, itr_stream_t stream);
 /* Re-order n lists of K candidates by new scores (evaluation.py:169, :209: the order np.argsort(...)[::-1] gives these K
  * candidates): idx [n, K] candidates, val [n, K] their new scores -> idx_out / val_out in the ranker's order (larger score
  * first, the higher index on exact ties, -0.0 == +0.0, NaN as +inf; of two entries with the same candidate and score the one
