@@ -157,6 +157,8 @@ SIGNATURES = {
     "itr_sgt_seg_smry_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "itr_embed_scatter_add": (i32, [vp, vp, i64, i64, i32, vp, vp]),
     "itr_gather_rows": (i32, [vp, i64, vp, i64, i32, vp, vp, vp]),
+    "itr_collate_batch": (i32, [vp, vp, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp,
+                                vp, vp]),
     "itr_sq_sum_blocks": (i32, [i64]),
     "itr_sq_sum": (i32, [vp, i64, vp, vp]),
     "itr_clip_coef": (i32, [vp, i64, f32, vp, vp]),

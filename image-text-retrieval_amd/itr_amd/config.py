@@ -26,7 +26,10 @@ DEFAULTS = dict(
     rnn_type='gru', bidirectional=0, dim_hidden=512, dim_vid=2048, input_dropout_p=0.2, rnn_dropout_p=0.5,
     dim_word=300, max_len=60, module_name='SGR', sgr_step=3, max_violation=False, margin=0.2, cross_attn="t2i",
     raw_feature_norm="clipped_l2norm", agg_func="LogSumExp", lambda_lse=6, lambda_softmax=9., smry_k=12,
-    smry_lamda=0.01, lr_decay_gamma=0.1, drop=0.0)
+    smry_lamda=0.01, lr_decay_gamma=0.1, drop=0.0,
+    # not a key of the reference: True keeps the training split in device memory and collates every batch there
+    # (datamodule/resident.py); False is the reference's DataLoader path
+    resident_data=False)
 
 NAMED = {
     'VSE_PP': dict(name="VSE++", data_name="f30k_precomp", vocab_type='pkl', val_step=10, img_dim=4096,

@@ -224,7 +224,16 @@ def get_loaders(data_name, batch_size, workers, config):
     if not config['data_name'].endswith('_precomp'):
         raise NotImplementedError("raw-image datasets (CocoDataset / FlickrDataset) are outside the precomp hot path")
     dpath = os.path.join(config['data_path'], data_name)
-    train_loader, vocab_size = get_precomp_loader(dpath, 'train', config, batch_size, True, workers)
+    if config.get('resident_data'):
+        # opt-in: the split lives in HBM and every batch is gathered there (resident.py); same batches as the loader below
+        from .resident import ResidentLoader, ResidentTrainSet
+        if not torch.cuda.is_available():
+            raise RuntimeError("resident_data=True keeps the training split in GPU memory: no CPU fallback")
+        dset = PrecompDataset(dpath, 'train', config)
+        train_loader = ResidentLoader(ResidentTrainSet(dset, torch.device('cuda', torch.cuda.current_device())), batch_size, True,
+                                      config.get('seed'))
+    else:
+        train_loader, vocab_size = get_precomp_loader(dpath, 'train', config, batch_size, True, workers)
     val_loader, vocab_size = get_precomp_loader(dpath, 'dev', config, batch_size, False, workers)
     return train_loader, val_loader, vocab_size
 

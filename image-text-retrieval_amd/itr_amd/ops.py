@@ -1833,3 +1833,93 @@ def rerank_lists(idx, val):
         return io, vo, po
     _lib.check(lib.itr_rerank_lists(_p(idx), _p(val), n, K, _p(io), _p(vo), _p(po), _stream()))
     return io, vo, po
+
+
+class CollatedBatch(object):
+    """What collate_batch wrote: `images`, `boxes`, `img_wh`, `ids` (ragged form), `tables` (tuple, fixed-width form),
+    `float_table`, each None when its source was not given, and the device int32 `bad_flag`."""
+    __slots__ = ("images", "boxes", "img_wh", "ids", "tables", "float_table", "bad_flag")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def collate_batch(feat, img_idx, boxes=None, img_wh=None, cap_idx=None, packed=None, off=None, lmax=None, tables=(), float_table=None,
+                  bad_flag=None, check=False):
+    """One training batch gathered from device-resident tables in one launch (itr_collate_batch): the device form of
+    PrecompDataset.__getitem__ + collate_fn for sample indices that are already in collate order.
+
+    feat [n_img, ...] float32 and img_idx int64 [B] -> images [B, ...]; boxes [n_img, ...] / img_wh [n_img, 2] follow img_idx.
+    Ragged caption ids: packed int64 [n], off int64 [n_cap + 1], cap_idx int64 [B], lmax -> ids int64 [B, lmax], zero padded.
+    Fixed-width caption tables: up to three int64 `tables` [n_cap, W] and one float32 `float_table` [n_cap, W] follow cap_idx.
+    An index outside its table reads row 0 and raises the device flag; the flag is read (a host synchronisation) only with
+    check=True, which then raises IndexError.  bad_flag: a zeroed device int32 to reuse over calls (default: a fresh one)."""
+    lib = _lib.load()
+    feat = _dev(feat, name="feat")
+    img_idx = _dev(img_idx, torch.int64, name="img_idx")
+    if feat.dim() < 1 or img_idx.dim() != 1 or feat.shape[0] < 1:
+        raise ValueError("collate_batch: feat must be [n_img >= 1, ...] and img_idx 1-D, got %s and %s" % (tuple(feat.shape), tuple(img_idx.shape)))
+    dev, B, n_img = feat.device, img_idx.shape[0], feat.shape[0]
+    tables = tuple(tables)
+    if len(tables) > 3:
+        raise ValueError("collate_batch: at most three int64 tables, got %d" % len(tables))
+    ragged = packed is not None or off is not None
+    fixed = tables + ((float_table,) if float_table is not None else ())
+    n_cap = 0
+    if ragged or fixed:
+        if cap_idx is None:
+            raise ValueError("collate_batch: caption tables need cap_idx")
+        cap_idx = _dev(cap_idx, torch.int64, name="cap_idx")
+        if cap_idx.shape != img_idx.shape:
+            raise ValueError("collate_batch: cap_idx %s vs img_idx %s" % (tuple(cap_idx.shape), tuple(img_idx.shape)))
+
+    def table(t, dtype, name, rows):
+        t = _dev(t, dtype, name=name)
+        if t.dim() < 1 or t.shape[0] != rows:
+            raise ValueError("collate_batch: %s must have %d rows, got %s" % (name, rows, tuple(t.shape)))
+        return t, torch.empty((B,) + tuple(t.shape[1:]), device=dev, dtype=dtype)
+
+    images = torch.empty((B,) + tuple(feat.shape[1:]), device=dev, dtype=torch.float32)
+    row_elems = feat[0].numel()
+    boxes, boxes_out = table(boxes, torch.float32, "boxes", n_img) if boxes is not None else (None, None)
+    if img_wh is not None:
+        img_wh, wh_out = table(img_wh, torch.float32, "img_wh", n_img)
+        if img_wh[0].numel() != 2:
+            raise ValueError("collate_batch: img_wh must be [n_img, 2], got %s" % (tuple(img_wh.shape),))
+    else:
+        wh_out = None
+    ids_out, n_packed = None, 0
+    if ragged:
+        if packed is None or off is None or lmax is None:
+            raise ValueError("collate_batch: ragged ids need packed, off and lmax")
+        packed, off = _dev(packed, torch.int64, name="packed"), _dev(off, torch.int64, name="off")
+        if packed.dim() != 1 or off.dim() != 1 or off.shape[0] < 2 or int(lmax) < 0:
+            raise ValueError("collate_batch: packed and off must be 1-D with off of n_cap + 1 >= 2 entries, lmax >= 0")
+        n_cap, n_packed = off.shape[0] - 1, packed.shape[0]
+        ids_out = torch.empty(B, int(lmax), device=dev, dtype=torch.int64)
+    W, pairs = 0, []
+    for k, t in enumerate(fixed):
+        if not n_cap:
+            n_cap = t.shape[0] if torch.is_tensor(t) and t.dim() == 2 else 0
+        src, dst = table(t, torch.int64 if k < len(tables) else torch.float32, "tables[%d]" % k if k < len(tables) else "float_table", n_cap)
+        if src.dim() != 2 or (pairs and src.shape[1] != W):
+            raise ValueError("collate_batch: the fixed-width tables must be 2-D of one width, got %s" % (tuple(src.shape),))
+        W = src.shape[1]
+        pairs.append((src, dst))
+    ipairs = pairs[:len(tables)] + [(None, None)] * (3 - len(tables))
+    fpair = pairs[len(tables)] if float_table is not None else (None, None)
+    if bad_flag is None:
+        bad_flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    else:
+        bad_flag = _dev(bad_flag, torch.int32, name="bad_flag")
+    if B:      # (the tensors of an empty batch have no storage to point at)
+        _lib.check(lib.itr_collate_batch(_p(img_idx), _p(cap_idx) if (ragged or fixed) else None, B, _p(feat), n_img, row_elems, _p(images),
+                                         _p(boxes), boxes[0].numel() if boxes is not None else 0, _p(boxes_out), _p(img_wh), _p(wh_out),
+                                         _p(packed) if ragged else None, n_packed, _p(off) if ragged else None, n_cap, int(lmax) if ragged else 0,
+                                         _p(ids_out), _p(ipairs[0][0]), _p(ipairs[1][0]), _p(ipairs[2][0]), _p(fpair[0]), W, _p(ipairs[0][1]),
+                                         _p(ipairs[1][1]), _p(ipairs[2][1]), _p(fpair[1]), _p(bad_flag), _stream()))
+    if check and int(bad_flag.item()):
+        raise IndexError("collate_batch: an index lies outside its table (img_idx vs %d image rows, cap_idx vs %d captions)" % (n_img, n_cap))
+    return CollatedBatch(images=images, boxes=boxes_out, img_wh=wh_out, ids=ids_out, tables=tuple(d for _, d in pairs[:len(tables)]),
+                         float_table=fpair[1], bad_flag=bad_flag)

@@ -606,6 +606,30 @@ int itr_embed_scatter_add(const int64_t *tokens, const float *dx, int64_t n_tok,
  * outside [0, V) read row 0 and set *bad_flag (device int) to 1. */
 int itr_gather_rows(const int64_t *idx, int64_t n, const float *table, int64_t V, int E, float *out, int *bad_flag,
                     itr_stream_t stream);
+/* One training batch assembled in ONE launch from tables that stay in device memory: the arithmetic of PrecompDataset.__getitem__
+ * (itr/datamodule/data_loader.py:104-131) and collate_fn (itr/datamodule/data_loader.py:134-178) for B samples whose indices are
+ * already in collate order (sorted by caption length, descending, stable).  A pure copy; nothing is allocated.
+ *   images_out[b, :] = feat[img_idx[b], :]          row_elems = R * img_dim floats per row, feat [n_img, row_elems]
+ *   boxes_out[b, :]  = boxes[img_idx[b], :]         box_elems = R * 4 floats    (boxes / boxes_out both NULL: skipped)
+ *   wh_out[b, :]     = img_wh[img_idx[b], :]        2 floats                    (img_wh / wh_out both NULL: skipped)
+ *   ragged ids (GRU families; packed / off / ids_out all NULL: skipped): caption c = cap_idx[b] owns the int64 ids
+ *       packed[off[c] .. off[c + 1]) of packed[n_packed], off[n_cap + 1]; ids_out[b, :] (Lmax int64) = those ids, then zeros
+ *       (the `targets` loop of collate_fn); ids beyond Lmax are dropped
+ *   fixed-width ids (BERT families, VSRN): out_k[b, :] = tab_k[cap_idx[b], :] for up to three int64 tables [n_cap, W] (ids, mask,
+ *       type ids) and fout[b, :] = ftab[cap_idx[b], :] for one float table [n_cap, W] (VSRN's mask); each pair may be NULL
+ * A row is moved with 16-byte loads and stores when its byte length is a multiple of 16 and both bases are 16-byte aligned,
+ * otherwise element by element (a slower path, not an error).  cap_idx may be NULL when no caption table is given.
+ * An index outside [0, n_img) / [0, n_cap) reads row 0 and sets *bad_flag (device int) to 1, as itr_gather_rows does; so does a
+ * ragged row whose offsets leave packed[] (it is written as zeros).
+ * Checked on the host before any launch: null pointers (a table without its output or the reverse included) and negative sizes
+ * -> ITR_ERR_BADARG; B, Lmax or a row width that needs more workgroups than one grid holds -> ITR_ERR_UNSUPPORTED; B == 0 ->
+ * ITR_OK, nothing launched.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+int itr_collate_batch(const int64_t *img_idx, const int64_t *cap_idx, int64_t B, const float *feat, int64_t n_img, int64_t row_elems,
+                      float *images_out, const float *boxes, int64_t box_elems, float *boxes_out, const float *img_wh, float *wh_out,
+                      const int64_t *packed, int64_t n_packed, const int64_t *off, int64_t n_cap, int64_t Lmax, int64_t *ids_out,
+                      const int64_t *tab0, const int64_t *tab1, const int64_t *tab2, const float *ftab, int64_t W, int64_t *out0,
+                      int64_t *out1, int64_t *out2, float *fout, int *bad_flag, itr_stream_t stream);
 /* clip_grad_norm_ (Models.py:223-224): itr_sq_sum writes itr_sq_sum_blocks(n) partial sums of squares of one gradient
  * tensor; itr_clip_coef turns all partials of all tensors into coef_and_norm[0] = min(1, max_norm / (||g|| + 1e-6)),
  * coef_and_norm[1] = ||g|| (device floats). */
