@@ -14,7 +14,7 @@
 //     dgi[row] = (dr, dz, dn)       dgh[row] = (dr, dz, dn r)          carry[b] = dh z  (+)= dgh W_hh   (MFMA GEMM)
 // then, over ALL tokens at once (MFMA GEMMs on transposed operands):
 //     dW_hh = dgh^T H_prev    db_hh = colsum(dgh)    dW_ih = dgi^T X    db_ih = colsum(dgi)    dX (+)= dgi W_ih
-// and dE[token] += dX (atomic scatter; the only non-deterministic summation order of the step).
+// and dE[token] += dX (itr_embed_scatter_add: the rows of a token in row order, no atomics -- the step has a fixed summation order).
 #include "itr_internal.h"
 #include "side_stream.h"
 

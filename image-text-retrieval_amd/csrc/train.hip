@@ -10,6 +10,7 @@
 //   itr_sq_sum                             partial sums of squares        (clip_grad_norm_, Models.py:223-224)
 //   itr_adam_step                          torch.optim.Adam update (no weight decay, no amsgrad), gradient pre-scaled
 #include "itr_common.h"
+#include <stdlib.h>
 
 namespace itr {
 
@@ -103,12 +104,56 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float *__restri
 }
 
 // ---------------------------------------------------------------- embedding backward
+// One workgroup per row; the workgroup of a token's FIRST row adds all rows of that token, in row order, and the others leave: a sum of a
+// fixed order without atomics (with atomicAdd two runs of one training step differed in the last bits, so no run could be replayed
+// bit for bit).  Every wave walks the token list 256 rows at a time (four loads in flight per lane); a thread keeps four columns
+// 128 apart, so up to 512 columns take one walk.
 __global__ __launch_bounds__(128) void embed_scatter_add_kernel(const int64_t *__restrict__ tokens, const float *__restrict__ dx,
                                                                 int64_t n_tok, int64_t V, int E, float *__restrict__ dE) {
     const int64_t row = blockIdx.x;
     const int64_t id = tokens[row];
     if (id < 0 || id >= V) return;
-    for (int k = threadIdx.x; k < E; k += 128) atomicAdd(dE + id * E + k, dx[row * E + k]);
+    const int lane = threadIdx.x & 63;
+    for (int64_t base = 0; base < row; base += 256) {            // an earlier row with this token owns the sum
+        bool hit = false;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t r = base + 64 * u + lane;
+            hit |= r < row && tokens[r] == id;
+        }
+        if (__ballot(hit)) return;
+    }
+    for (int k0 = 0; k0 < E; k0 += 512) {
+        float acc[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int k = k0 + 128 * c + threadIdx.x;
+            acc[c] = k < E ? dE[id * E + k] + dx[row * E + k] : 0.f;
+        }
+        for (int64_t base = row + 1; base < n_tok; base += 256) {
+            unsigned long long m[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int64_t r = base + 64 * u + lane;
+                m[u] = __ballot(r < n_tok && tokens[r] == id);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                for (unsigned long long mm = m[u]; mm; mm &= mm - 1) {
+                    const int64_t r = base + 64 * u + __builtin_ctzll(mm);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int k = k0 + 128 * c + threadIdx.x;
+                        if (k < E) acc[c] += dx[r * E + k];
+                    }
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int k = k0 + 128 * c + threadIdx.x;
+            if (k < E) dE[id * E + k] = acc[c];
+        }
+    }
 }
 
 // ---------------------------------------------------------------- optimizer
@@ -125,15 +170,18 @@ __global__ __launch_bounds__(256) void sq_sum_kernel(const float *__restrict__ g
 // p, m, v updated in place.  torch.optim.Adam (single-tensor path):
 //   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // `gscale` carries clip_grad_norm_'s coefficient min(1, max_norm / (total_norm + 1e-6)).
+// omb1 / omb2 = 1 - beta as torch forms them: in double from the decimal the user wrote, then rounded to float.  1.f - 0.999f is
+// 0.99998713e-3, a relative 1.3e-5 off in every element of v (tests/test_train_primitives_gpu.py: test_adam_with_clipping).
 __global__ __launch_bounds__(256) void adam_step_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                         float *__restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
-                                                        float bc1, float bc2_sqrt, const float *__restrict__ gscale_dev) {
+                                                        float omb1, float omb2, float bc1, float bc2_sqrt,
+                                                        const float *__restrict__ gscale_dev) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float gs = gscale_dev ? gscale_dev[0] : 1.f;
     const float gi = g[i] * gs;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi;
     v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -165,15 +213,16 @@ __global__ __launch_bounds__(256) void sq_sum_multi_kernel(const OptTensor *__re
 }
 __global__ __launch_bounds__(256) void adam_step_multi_kernel(const OptTensor *__restrict__ tab, const int32_t *__restrict__ blk_tensor,
                                                               const int32_t *__restrict__ blk_first, float lr, float b1, float b2, float eps,
-                                                              float bc1, float bc2_sqrt, const float *__restrict__ gscale_dev) {
+                                                              float omb1, float omb2, float bc1, float bc2_sqrt,
+                                                              const float *__restrict__ gscale_dev) {
     const int ti = blk_tensor[blockIdx.x];
     const OptTensor t = tab[ti];
     const int64_t i = ((int64_t)blockIdx.x - blk_first[ti]) * 256 + threadIdx.x;
     if (i >= t.n) return;
     const float gs = gscale_dev ? gscale_dev[0] : 1.f;
     const float gi = t.g[i] * gs;
-    const float mi = b1 * t.m[i] + (1.f - b1) * gi;
-    const float vi = b2 * t.v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * t.m[i] + omb1 * gi;
+    const float vi = b2 * t.v[i] + omb2 * gi * gi;
     t.m[i] = mi;
     t.v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -197,6 +246,15 @@ __global__ __launch_bounds__(64) void clip_coef_kernel(const float *__restrict__
 }  // namespace itr
 
 using namespace itr;
+
+// A float beta stands for the short decimal the user wrote (0.9, 0.999).  torch holds that decimal as a double and forms 1 - beta and the
+// bias corrections 1 - beta^t from it; so does this: a beta that six digits do not reproduce stands for itself.
+static double beta_decimal(float beta) {
+    char buf[32];
+    snprintf(buf, sizeof buf, "%.6g", (double)beta);
+    const double d = strtod(buf, nullptr);
+    return (float)d == beta ? d : (double)beta;
+}
 
 extern "C" int itr_l2norm_fwd_save(const float *x, float *z, float *norms, int64_t rows, int dim, float eps, itr_stream_t stream) {
     ITR_REQUIRE(x && z && norms, "itr_l2norm_fwd_save: null pointer");
@@ -286,10 +344,11 @@ extern "C" int itr_adam_step(float *p, const float *g, float *m, float *v, int64
     ITR_REQUIRE(p && g && m && v, "itr_adam_step: null pointer");
     ITR_REQUIRE(n >= 0 && step >= 1, "itr_adam_step: bad size / step");
     if (n == 0) return ITR_OK;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    const double d1 = beta_decimal(beta1), d2 = beta_decimal(beta2);
+    const double bc1 = 1.0 - pow(d1, (double)step);
+    const double bc2 = 1.0 - pow(d2, (double)step);
     hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), p, g, m, v, n, lr, beta1, beta2,
-                       eps, (float)bc1, (float)sqrt(bc2), grad_scale_dev);
+                       eps, (float)(1.0 - d1), (float)(1.0 - d2), (float)bc1, (float)sqrt(bc2), grad_scale_dev);
     ITR_CHECK_LAUNCH("adam_step");
     return ITR_OK;
 }
@@ -312,10 +371,12 @@ extern "C" int itr_adam_step_multi(const void *table_dev, const int32_t *blk_ten
     ITR_REQUIRE(n_blocks >= 0 && n_blocks <= 0x7fffffff && step >= 1, "itr_adam_step_multi: bad size / step");
     if (n_blocks == 0) return ITR_OK;
     ITR_REQUIRE(table_dev && blk_tensor_dev && blk_first_dev, "itr_adam_step_multi: null pointer");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    const double d1 = beta_decimal(beta1), d2 = beta_decimal(beta2);
+    const double bc1 = 1.0 - pow(d1, (double)step);
+    const double bc2 = 1.0 - pow(d2, (double)step);
     hipLaunchKernelGGL(adam_step_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, as_stream(stream), static_cast<const OptTensor *>(table_dev),
-                       blk_tensor_dev, blk_first_dev, lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale_dev);
+                       blk_tensor_dev, blk_first_dev, lr, beta1, beta2, eps, (float)(1.0 - d1), (float)(1.0 - d2), (float)bc1, (float)sqrt(bc2),
+                       grad_scale_dev);
     ITR_CHECK_LAUNCH("adam_step_multi");
     return ITR_OK;
 }

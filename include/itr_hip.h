@@ -599,7 +599,7 @@ int itr_sgt_seg_smry_fwd(const float *logit, const float *words, const int32_t *
                          itr_stream_t stream);
 int itr_sgt_seg_smry_bwd(const float *p, const float *words, const float *dout, const int32_t *cap_off, int C, int D, int Wmax, float *dlogit,
                          float *dwords, itr_stream_t stream);
-/* nn.Embedding backward: dE[tokens[r], :] += dx[r, :] (atomic adds). */
+/* nn.Embedding backward: dE[tokens[r], :] += dx[r, :]; the rows of one token are added in row order (no atomics: the same bits every run). */
 int itr_embed_scatter_add(const int64_t *tokens, const float *dx, int64_t n_tok, int64_t V, int E, float *dE,
                           itr_stream_t stream);
 /* out[r, :] = table[idx[r], :]  (nn.Embedding forward; the last-valid-step gather of TextEncoder.py:57-60).  Indices
@@ -637,7 +637,10 @@ int itr_sq_sum_blocks(int64_t n);
 int itr_sq_sum(const float *g, int64_t n, float *partials, itr_stream_t stream);
 int itr_clip_coef(const float *partials, int64_t nparts, float max_norm, float *coef_and_norm, itr_stream_t stream);
 /* torch.optim.Adam step on one tensor (no weight decay / amsgrad); the gradient is multiplied by *grad_scale_dev
- * (device float, may be NULL) first; `step` is the 1-based update count. */
+ * (device float, may be NULL) first; `step` is the 1-based update count.  A float beta stands for the decimal of at most six digits that
+ * rounds to it (0.9f for 0.9, 0.999f for 0.999): 1 - beta and the bias corrections 1 - beta^step are formed in double from that decimal,
+ * as torch forms them from the double it holds; a beta that six digits do not reproduce stands for itself.  (1.f - 0.999f is a relative
+ * 1.3e-5 away from 1 - 0.999.)  The same holds for itr_adam_step_multi. */
 int itr_adam_step(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
                   int64_t step, const float *grad_scale_dev, itr_stream_t stream);
 

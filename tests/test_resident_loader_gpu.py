@@ -127,23 +127,19 @@ def _check_parity(loader_1, loader_2, resident):
     """The yardstick is the DataLoader path run twice from one seed: the resident run may differ from the first of them by no
     more than the second does -- bit for bit where those two agree bit for bit.
 
-    Measured (MI355X, toy epoch of 5 steps, largest |difference| of the per-step losses / of the final parameters).  The batches
-    of the two paths are bit-identical (test_batches_equal_the_loaders), but the training step itself is not run-to-run
-    deterministic: the embedding gradient is an atomic scatter (csrc/gru_train.hip), so two DataLoader runs differ in the last
-    bits, and all three runs are draws of one distribution:
-        VSE++            loader-loader 2.4e-07 / 3.0e-08    resident-loader 2.4e-07 / 3.0e-08, then 6.0e-08 / 1.5e-08
-        SCAN   1st run   loader-loader 4.8e-07 / 1.19e-07   resident-loader 4.8e-07 / 1.32e-07   (parameters: missed by 1.2e-08)
-        SCAN   2nd run   loader-loader 4.8e-07 / 1.64e-07   resident-loader 4.8e-07 / 1.04e-07   (met)
-        2 gloo ranks     loader-loader 4.8e-07 / 8.2e-08    resident-loader 2.4e-07 / 3.0e-08    (met)
-    and in the run of the whole suite: VSE++ loader-loader 0 / 3.0e-08, resident-loader 2.4e-07 / 3.0e-08 (loss: missed by one
-    ulp of the loss); 2 gloo ranks loader-loader 3.6e-07 / 1.19e-07, resident-loader 4.8e-07 / 1.64e-07 (missed); SCAN met.
-    The comparison is kept as specified (no factor on the yardstick), so it misses by rounding noise of this size about as
-    often as it is met: a miss here says nothing about the batches, which the equality test above pins bit for bit."""
+    The batches of the two paths are bit-identical (test_batches_equal_the_loaders) and the training step is deterministic -- the
+    embedding gradient, once an atomic scatter whose last bits changed from run to run, adds the rows of a token in row order
+    (csrc/train.hip) -- so the two DataLoader runs agree bit for bit, which is asserted, and the resident run has to as well.
+
+    Record of the atomic scatter (MI355X, toy epoch of 5 steps, largest |difference| of the per-step losses / of the final
+    parameters): two DataLoader runs differed by 0 .. 4.8e-07 / 3.0e-08 .. 1.64e-07 and the resident run by as much from either, so
+    this comparison, which puts no factor on the yardstick, missed by rounding noise about as often as it was met."""
     assert str(loader_1[2]) == str(loader_2[2]) == 'DataLoader' and str(resident[2]) == 'ResidentLoader'
     assert len(loader_1[0]) == 5 and np.isfinite(loader_1[0]).all() and np.isfinite(resident[1]).all()
     d_loss, d_par = _differ(loader_1, loader_2)
     r_loss, r_par = _differ(loader_1, resident)
     print("loader vs loader: dloss %.3e dparam %.3e; resident vs loader: dloss %.3e dparam %.3e" % (d_loss, d_par, r_loss, r_par))
+    assert d_loss == 0 and d_par == 0, (d_loss, d_par)          # the step is deterministic
     assert r_loss <= d_loss and r_par <= d_par, (r_loss, d_loss, r_par, d_par)
     if d_loss == 0 and d_par == 0:
         assert np.array_equal(loader_1[0], resident[0]) and np.array_equal(loader_1[1].view(np.uint32), resident[1].view(np.uint32))
