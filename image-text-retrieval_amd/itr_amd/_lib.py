@@ -126,6 +126,7 @@ SIGNATURES = {
     "itr_scan_pair_attention": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, i64, vp, vp, i64,
                                       vp, vp, sz, vp]),
     "itr_rerank_lists": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
+    "itr_rerank_fuse_lists": (i32, [vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]),
     # ---- training step
     "itr_l2norm_fwd_save": (i32, [vp, vp, vp, i64, i32, f32, vp]),
     "itr_l2norm_bwd": (i32, [vp, vp, vp, vp, i64, i32, f32, vp]),

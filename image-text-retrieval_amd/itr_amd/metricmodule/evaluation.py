@@ -653,3 +653,163 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
     if sgraf_m is not None:
         np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_explain{sgraf_m}_sgraf.npz'), **reasoned)
     return res_dic
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Ensemble reranking: several fine models score the same shortlists, the lists are re-ordered by the float64 mean of their scores
+# (ops.rerank_fused_lists) -- evalrank_ensemble's average (evaluation.py:377-381) restricted to the listed pairs.
+def _is_factory(f):
+    """A zero-argument factory of a score_fn (as opposed to a score_fn, which takes (cand, by))"""
+    import inspect
+    try:
+        params = inspect.signature(f).parameters.values()
+    except (TypeError, ValueError):
+        return False
+    return not any(p.default is p.empty and p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD) for p in params)
+
+
+def rerank_ensemble(sims_coarse, score_fns, k, im_div=5):
+    """`rerank` with an ensemble of 1 to 4 fine models: the k-lists of both directions come from the coarse matrix exactly as in
+    `rerank`, every member scores the same two lists, and ops.rerank_fused_lists re-orders them by the fused score -- the float64
+    sum of the members' scores in the order given, divided by their number (evalrank_ensemble's average on the listed pairs).
+    score_fns: a sequence of `score_fn(cand, by)` as `rerank` takes them, or of zero-argument factories returning one: a member's
+    device state is then built, used for both directions and released before the next member's is built.
+    -> `rerank`'s tuple; in lists, 'i2t_topk_scores' / 't2i_topk_scores' are the float64 fused scores and 'i2t_topk_member_scores'
+    / 't2i_topk_member_scores' (float32 [M, n, k]) what each member gave the entries, in the reranked order."""
+    k = int(k)
+    if k < 10:
+        raise ValueError("rerank_ensemble: k = %d < 10: R@10 would not be defined by the shortlist" % k)
+    score_fns = list(score_fns)
+    if not 1 <= len(score_fns) <= 4:
+        raise ValueError("rerank_ensemble: 1 to 4 fine members, got %d" % len(score_fns))
+    S = _device_matrix(sims_coarse)
+    if S.dtype != torch.float32:
+        S = S.to(torch.float32)
+    r_idx, _, part = ops.topk_lists(S, k)
+    c_idx, _ = ops.topk_merge_cols([part], k)
+    i_rank, _, t_rank, _, _ = ops.rank_counts(S, im_div)
+    fine_i, fine_t = [], []
+    for f in score_fns:
+        fn = f() if _is_factory(f) else f
+        fine_i.append(fn(r_idx, 'image'))
+        fine_t.append(fn(c_idx, 'caption'))
+        del fn                                # a factory's state goes before the next member's is built
+    ri, rf, rv, _ = ops.rerank_fused_lists(r_idx, fine_i)
+    ci, cf, cv, _ = ops.rerank_fused_lists(c_idx, fine_t)
+    lists = {'i2t_topk': ri.cpu().numpy().astype(np.int64), 'i2t_topk_scores': rf.cpu().numpy(),
+             'i2t_topk_member_scores': rv.cpu().numpy(),
+             't2i_topk': ci.cpu().numpy().astype(np.int64), 't2i_topk_scores': cf.cpu().numpy(),
+             't2i_topk_member_scores': cv.cpu().numpy()}
+    i_ranks = rerank_rank_vector(lists['i2t_topk'], i_rank.cpu().numpy(), 'i2t', im_div)
+    t_ranks = rerank_rank_vector(lists['t2i_topk'], t_rank.cpu().numpy(), 't2i', im_div)
+    return ops.recall_from_ranks(i_ranks), ops.recall_from_ranks(t_ranks), (i_ranks, t_ranks), lists
+
+
+def evalrank_rerank_ensemble(model_path_coarse, model_paths_fine, k, data_path=None, split='dev', fold5=False, explain=None,
+                             explain_sgraf=None):
+    """`evalrank_rerank` with an ensemble of 1 to 4 fine checkpoints, each SCAN (either cross_attn) or SGRAF (SAF or SGR), in any
+    mix: the coarse model shortlists k candidates per query in both directions, every fine model scores those pairs, the lists are
+    re-ordered by the float64 mean of the members' scores (`rerank_ensemble`; SAF + SGR is the published SGRAF, SCAN t2i + i2t the
+    published SCAN).  One member's device state exists at a time.  Writes `<data_name>[_5fold]_rerank<k>_ensemble_result.yaml`
+    ('coarse', 'rerank', 'k', 'data_name', 'modal_path_coarse', 'modal_paths_fine') and `<data_name>[_5fold]_rerank<k>_ensemble.npz`
+    (the reranked lists, their fused scores and every member's scores) next to the coarse checkpoint; evalrank_rerank's files
+    are not touched.
+    explain=M / explain_sgraf=M (1 <= M <= k, not with fold5): the fused best M results of every query are explained by every SCAN /
+    every SGRAF member (`explain` / `explain_sgraf` on the fused lists, one member at a time), member j (1-based position among
+    the fine checkpoints) in `<data_name>_rerank<k>_ensemble_explain<M>_member<j>.npz` / `..._member<j>_sgraf.npz`."""
+    import os
+    import yaml
+    from ..datamodule import data_loader as data
+    k = int(k)
+    if k < 10:
+        raise ValueError("evalrank_rerank_ensemble: k = %d < 10: R@10 would not be defined by the shortlist" % k)
+    model_paths_fine = [model_paths_fine] if isinstance(model_paths_fine, str) else list(model_paths_fine)
+    if not 1 <= len(model_paths_fine) <= 4:
+        raise ValueError("evalrank_rerank_ensemble: 1 to 4 fine checkpoints, got %d" % len(model_paths_fine))
+    wanted = {}
+    for name, m in (('explain', explain), ('explain_sgraf', explain_sgraf)):
+        if m is None:
+            continue
+        if fold5:
+            raise ValueError("evalrank_rerank_ensemble: %s does not combine with fold5" % name)
+        if int(m) < 1 or int(m) > k:
+            raise ValueError("evalrank_rerank_ensemble: %s = %d outside [1, k = %d]" % (name, int(m), k))
+        wanted[name] = int(m)
+    coarse, c_cfg = _load_for_eval(model_path_coarse, data_path)
+    fines = [_load_for_eval(p, data_path) for p in model_paths_fine]
+    for _, f_cfg in fines:
+        if f_cfg['name'] not in ('SCAN', 'SGRAF'):
+            raise NotImplementedError("evalrank_rerank_ensemble: every fine model must be SCAN or SGRAF (candidate-list scoring exists for "
+                                      "these only), got %s" % f_cfg['name'])
+    families = [f_cfg['name'] for _, f_cfg in fines]
+    if 'explain' in wanted and 'SCAN' not in families:
+        raise NotImplementedError("evalrank_rerank_ensemble: explain needs a SCAN member (attention maps exist for SCAN only; SGRAF members "
+                                  "explain themselves through explain_sgraf), got %s" % ', '.join(families))
+    if 'explain_sgraf' in wanted and 'SGRAF' not in families:
+        raise NotImplementedError("evalrank_rerank_ensemble: explain_sgraf needs an SGRAF member (SCAN members explain themselves through "
+                                  "explain), got %s" % ', '.join(families))
+    for _, f_cfg in fines:
+        if f_cfg['data_name'] != c_cfg['data_name']:
+            raise ValueError("evalrank_rerank_ensemble: the checkpoints name different datasets (%s, %s): their lists would not index the "
+                             "same items" % (c_cfg['data_name'], f_cfg['data_name']))
+    embs = []
+    for model, cfg in [(coarse, c_cfg)] + fines:
+        loader, _ = data.get_test_loader(split, cfg['data_name'], cfg['batch_size'], cfg['workers'], cfg)
+        embs.append(encode_data(model, loader, islength=cfg['name'] in ['SGRAF', 'SCAN']))
+    (c_img, c_cap, c_len), f_embs = embs[0], embs[1:]
+    for f_img, f_cap, _ in f_embs:
+        if len(c_img) != len(f_img) or len(c_cap) != len(f_cap):
+            raise ValueError("evalrank_rerank_ensemble: the models' loaders hold different item counts (%d / %d images, %d / %d captions)"
+                             % (len(c_img), len(f_img), len(c_cap), len(f_cap)))
+    lists = {}
+    explained = {}             # file suffix -> arrays
+
+    def block(sl_img, sl_cap, prefix):
+        sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
+        res_c = cal_recall(sims)
+
+        def factory(j):
+            make = _scan_score_fn if families[j] == 'SCAN' else _sgraf_score_fn
+            f_img, f_cap, f_len = f_embs[j]
+            return lambda: make(fines[j][0], f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
+        factories = [factory(j) for j in range(len(fines))]
+        r, ri, (i_ranks, t_ranks), tl = rerank_ensemble(sims.astype(np.float32), factories, k)
+        lists.update({prefix + key: v for key, v in tl.items()})
+        for j, family in enumerate(families):          # one member's state at a time, rebuilt for the explanation
+            if family == 'SCAN' and 'explain' in wanted:
+                fn = factories[j]()
+                explained['explain%d_member%d' % (wanted['explain'], j + 1)] = _explain_lists(tl, fn, wanted['explain'])
+                del fn
+            if family == 'SGRAF' and 'explain_sgraf' in wanted:
+                fn = factories[j]()
+                explained['explain%d_member%d_sgraf' % (wanted['explain_sgraf'], j + 1)] = _explain_sgraf_lists(tl, fn, wanted['explain_sgraf'])
+                del fn
+        res_r = _recall_dict((i_ranks, tl['i2t_topk'][:, 0], t_ranks, tl['t2i_topk'][:, 0]))
+        print("Ensemble of %d reranked (k = %d) image to text: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((len(fines), k) + tuple(r)))
+        print("Ensemble of %d reranked (k = %d) text to image: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((len(fines), k) + tuple(ri)))
+        return res_c, res_r
+
+    n = len(c_img)
+    if not fold5:
+        res_c, res_r = block(slice(0, n, 5), slice(None), '')
+        res_dic = {'coarse': res_c, 'rerank': res_r}
+    else:
+        res_dic = {'coarse': {'sum_result': []}, 'rerank': {'sum_result': []}}
+        for i in range(5):
+            res_c, res_r = block(slice(i * 5000, (i + 1) * 5000, 5), slice(i * 5000, (i + 1) * 5000), f'PART_{i + 1}_')
+            for key, part in (('coarse', res_c), ('rerank', res_r)):
+                res_dic[key][f'PART_{i + 1}'] = part
+                res_dic[key]['sum_result'] += part['result']
+        for key in ('coarse', 'rerank'):
+            res_dic[key]['Mean_metrics'] = _mean_metrics(res_dic[key])
+    res_dic['data_name'] = c_cfg['data_name'] + ('_5fold' if fold5 else '')
+    res_dic['k'] = k
+    res_dic['modal_path_coarse'], res_dic['modal_paths_fine'] = model_path_coarse, list(model_paths_fine)
+    save_dir = os.path.dirname(model_path_coarse)
+    stem = os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{k}_ensemble')
+    with open(stem + '_result.yaml', 'w') as f:
+        yaml.safe_dump(_plain(res_dic), f)
+    np.savez(stem + '.npz', **lists)
+    for suffix, arrays in explained.items():
+        np.savez(stem + '_' + suffix + '.npz', **arrays)
+    return res_dic

@@ -1835,6 +1835,41 @@ def rerank_lists(idx, val):
     return io, vo, po
 
 
+def rerank_fused_lists(idx, vals):
+    """Ensemble reranking: re-order K-lists by the mean of M models' scores.  idx int32 [n, K] candidates (in coarse order); vals a
+    sequence of M float32 [n, K] tensors or one [M, n, K] tensor, the members' scores of those candidates.  The fused score is the
+    float64 sum in member order divided by float64(M) (the reference's ensemble average on the listed pairs).
+    -> (idx_sorted int32 [n, K], fused float64 [n, K], vals_sorted float32 [M, n, K], perm int32 [n, K]) in the float64 ranker's
+    order (larger fused score first, the higher index on exact ties, -0.0 == +0.0, NaN as +inf; equal entries keep their coarse
+    order); perm = old position of each entry, member scores keep their bits.  1 <= K <= TOPK_MAX, 1 <= M <= 4."""
+    lib = _lib.load()
+    idx = _dev(idx, torch.int32, name="idx")
+    if torch.is_tensor(vals):
+        val = _dev(vals, torch.float32, name="vals")
+        if val.dim() != 3:
+            raise ValueError("rerank_fused_lists: a vals tensor must be [M, n, K], got %s" % (tuple(val.shape),))
+    else:
+        members = [_dev(v, torch.float32, name="vals[%d]" % m) for m, v in enumerate(vals)]
+        if not members:
+            raise ValueError("rerank_fused_lists: no member scores")
+        for m, v in enumerate(members):
+            if v.shape != members[0].shape or v.dim() != 2:
+                raise ValueError("rerank_fused_lists: every member's scores must be 2-D of one shape, got %s for member %d and %s for member 0"
+                                 % (tuple(v.shape), m, tuple(members[0].shape)))
+        val = torch.stack(members)
+    if idx.dim() != 2 or idx.shape != val.shape[1:]:
+        raise ValueError("rerank_fused_lists: idx must be [n, K] and vals [M, n, K], got %s and %s" % (tuple(idx.shape), tuple(val.shape)))
+    M = val.shape[0]
+    n, K = idx.shape
+    io, po = torch.empty_like(idx), torch.empty_like(idx)
+    fo = torch.empty((n, K), dtype=torch.float64, device=idx.device)
+    vo = torch.empty_like(val)
+    if n == 0:
+        return io, fo, vo, po
+    _lib.check(lib.itr_rerank_fuse_lists(_p(idx), _p(val), M, n, K, _p(io), _p(fo), _p(vo), _p(po), _stream()))
+    return io, fo, vo, po
+
+
 class CollatedBatch(object):
     """What collate_batch wrote: `images`, `boxes`, `img_wh`, `ids` (ragged form), `tables` (tuple, fixed-width form),
     `float_table`, each None when its source was not given, and the device int32 `bad_flag`."""

@@ -7,7 +7,11 @@ second (SCAN or SGRAF) scores only those  ->  <data_name>[_5fold]_rerank<K>_resu
 With --explain M (SCAN fine model): also the word-by-region attention maps, per-word / per-region similarities and scores of the
 best M results of every query  ->  <data_name>_rerank<K>_explain<M>.npz
 With --explain-sgraf M (SGRAF fine model): the word-by-region attention, SAF's filtration weights or SGR's graph edges of every
-step, and the scores of the best M results of every query  ->  <data_name>_rerank<K>_explain<M>_sgraf.npz"""
+step, and the scores of the best M results of every query  ->  <data_name>_rerank<K>_explain<M>_sgraf.npz
+python test.py COARSE_PATH FINE_1 FINE_2 [FINE_3 [FINE_4]] --rerank K: ensemble reranking, every fine model (SCAN or SGRAF, any mix; SAF + SGR
+is the published SGRAF, SCAN t2i + i2t the published SCAN) scores the shortlists and they are re-ordered by the float64 mean of the
+members' scores  ->  <data_name>[_5fold]_rerank<K>_ensemble_result.yaml and <data_name>[_5fold]_rerank<K>_ensemble.npz; with --explain M /
+--explain-sgraf M every SCAN / SGRAF member explains the fused best M  ->  <data_name>_rerank<K>_ensemble_explain<M>_member<j>[_sgraf].npz"""
 import argparse
 import os
 import sys
@@ -26,7 +30,9 @@ if __name__ == "__main__":
     ap.add_argument("--topk", type=int, default=0, metavar="K",
                     help="also write the top-K retrieved items of every query (indices and scores) to <data_name>..._top<K>.npz")
     ap.add_argument("--rerank", type=int, default=0, metavar="K",
-                    help="two checkpoints COARSE FINE: FINE (SCAN or SGRAF) re-scores only COARSE's top-K candidates of every query")
+                    help="two checkpoints COARSE FINE: FINE (SCAN or SGRAF) re-scores only COARSE's top-K candidates of every query; "
+                         "three to five checkpoints COARSE FINE_1 FINE_2 [FINE_3 [FINE_4]]: the fine models' scores of those candidates "
+                         "are averaged in float64 (ensemble reranking)")
     ap.add_argument("--explain", type=int, default=None, metavar="M",
                     help="with --rerank K and a SCAN fine model: also write the attention maps of the best M <= K results of every query")
     ap.add_argument("--explain-sgraf", type=int, default=None, metavar="M",
@@ -38,12 +44,16 @@ if __name__ == "__main__":
     if a.explain_sgraf is not None and not a.rerank:
         ap.error("--explain-sgraf needs --rerank K")
     if a.rerank:
-        if len(a.model_path) != 2:
-            ap.error("--rerank needs two checkpoints: COARSE FINE")
+        if not 2 <= len(a.model_path) <= 5:
+            ap.error("--rerank needs two checkpoints, COARSE FINE, or for an ensemble up to five: COARSE FINE_1 FINE_2 [FINE_3 [FINE_4]]")
         if a.fast or a.topk:
             ap.error("--rerank does not combine with --fast or --topk (the reranked lists are written to ..._rerank<K>.npz)")
-        evaluation.evalrank_rerank(a.model_path[0], a.model_path[1], a.rerank, data_path=a.data_path, split=a.split, fold5=a.fold5,
-                                   explain=a.explain, explain_sgraf=a.explain_sgraf)
+        if len(a.model_path) == 2:
+            evaluation.evalrank_rerank(a.model_path[0], a.model_path[1], a.rerank, data_path=a.data_path, split=a.split, fold5=a.fold5,
+                                       explain=a.explain, explain_sgraf=a.explain_sgraf)
+        else:
+            evaluation.evalrank_rerank_ensemble(a.model_path[0], a.model_path[1:], a.rerank, data_path=a.data_path, split=a.split,
+                                                fold5=a.fold5, explain=a.explain, explain_sgraf=a.explain_sgraf)
     elif a.fast:
         import torch
         import torch.distributed as dist

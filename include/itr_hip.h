@@ -512,6 +512,20 @@ int itr_sgraf_pair_attention(const float *img, const float *words, const int64_t
  * 1 <= K <= ITR_TOPK_MAX; outputs must not alias inputs. */
 int itr_rerank_lists(const int32_t *idx, const float *val, int64_t n, int K, int32_t *idx_out, float *val_out,
                      int32_t *perm_out, itr_stream_t stream);
+/* Ensemble reranking: fuse the scores of M fine models on the same n lists of K candidates and re-order the lists by the fused
+ * score.  idx [n, K] candidates in coarse order, val [M, n, K] the members' scores (member-major).  The fused score of an entry
+ * is  ((double)val[0] + (double)val[1] + ... + (double)val[M-1]) / (double)M , added in member order -- the reference's ensemble
+ * (sims + sims2) / 2 on float64 matrices (evaluation.py:377-381) restricted to the listed pairs -- and the order is the one
+ * np.argsort(...)[::-1] (evaluation.py:169, :209) gives these K candidates under it, by the float64 rule: larger fused score
+ * first, the higher index on exact ties, -0.0 == +0.0, NaN as +inf; of two entries with the same candidate and fused score the
+ * one that stood first stays first.  idx_out [n, K], fused_out [n, K] (the computed doubles unchanged: a NaN stays NaN), val_out
+ * [M, n, K] or NULL (member scores in the new order, original bits), perm_out [n, K] = old position of each entry.  With M = 1
+ * idx_out and perm_out are itr_rerank_lists'; with M = 2 swapping the members changes no bit of idx_out, fused_out, perm_out.
+ * 1 <= K <= ITR_TOPK_MAX, 1 <= M <= ITR_RERANK_MAX_MEMBERS (ITR_ERR_UNSUPPORTED above); outputs must not alias inputs.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+#define ITR_RERANK_MAX_MEMBERS 4
+int itr_rerank_fuse_lists(const int32_t *idx, const float *val, int M, int64_t n, int K, int32_t *idx_out, double *fused_out,
+                          float *val_out, int32_t *perm_out, itr_stream_t stream);
 
 /* ---- a14: the training step  model.train_emb (itr/modalmodule/Models.py:198-225, :115-145): forward -> loss ->
  * backward -> clip_grad_norm_(2.0) -> Adam.  Backward contractions are itr_gemm_nt on transposed operands;
