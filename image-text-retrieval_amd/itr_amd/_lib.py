@@ -109,6 +109,8 @@ SIGNATURES = {
     "itr_topk": (i32, [vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, sz, vp]),
     "itr_topk_merge": (i32, [vp, vp, i32, i64, i32, i32, vp, vp, vp]),
     "itr_topk_f64": (i32, [vp, i64, i64, i64, i32, vp, vp, vp, vp, vp]),
+    "itr_topk_fold_workspace_bytes": (sz, [i64, i64, i32]),
+    "itr_topk_fold_cols": (i32, [vp, i64, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
     "itr_scan_pairs_workspace_bytes": (sz, [i64, i32, i64, i64, i32]),
     "itr_scan_pairs_prepare": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, sz, vp]),
     "itr_sgraf_pairs_state_bytes": (sz, [i64, i64, i64, i32, i32, i32, i32]),

@@ -498,6 +498,25 @@ def exchange_score(comm, img, send, ranges, n_cap_total, score_fn, timers=None):
     return S
 
 
+def _stream_rows_per_block(Nc, budget_bytes, rows_per_block):
+    """Rows of a streamed block: the caller's, or what fits the byte budget in multiples of 128 (at least 128)."""
+    return rows_per_block or max(128, (budget_bytes // (4 * max(Nc, 1))) // 128 * 128)
+
+
+def _stream_band_gt(img, cap, score_fn, im_div, rb, buf):
+    """First pass of the streamed forms: the diagonal band (a block's rows x their im_div x rows captions) through the reused buffer
+    -> the ground-truth score of every caption, bit-identical to the band's elements of the full rows."""
+    Ni, Nc = img.shape[0], cap.shape[0]
+    s_gt = torch.full((Nc,), float('-inf'), device=img.device, dtype=torch.float32)
+    for r0 in range(0, Ni, rb):
+        r1 = min(Ni, r0 + rb)
+        c0, c1 = min(Nc, r0 * im_div), min(Nc, r1 * im_div)
+        if c1 > c0:
+            band = score_fn(img[r0:r1], cap[c0:c1], out=buf[:(r1 - r0) * (c1 - c0)].view(r1 - r0, c1 - c0))
+            ops.gather_gt(band, im_div, 0, s_gt[c0:c1])
+    return s_gt
+
+
 def score_rank_streamed(img, cap, score_fn, im_div=5, budget_bytes=64 << 20, rows_per_block=None, timers=None):
     """One process, pooled scorers: the Recall ranks of score_fn(img, cap) WITHOUT the similarity matrix in HBM (SURVEY 7 step 3, 2.3 K4
     "fuse with K9"; the reference builds the full float64 matrix and argsorts it, evaluation.py:124-153, :169, :209).
@@ -516,17 +535,11 @@ def score_rank_streamed(img, cap, score_fn, im_div=5, budget_bytes=64 << 20, row
     -> the tuple finalize_ranks returns."""
     Ni, Nc = img.shape[0], cap.shape[0]
     dev = img.device
-    rb = rows_per_block or max(128, (budget_bytes // (4 * max(Nc, 1))) // 128 * 128)
+    rb = _stream_rows_per_block(Nc, budget_bytes, rows_per_block)
     if timers is not None:
         timers['scan_start'].record()
     buf = torch.empty(min(rb, Ni) * Nc, device=dev, dtype=torch.float32)
-    s_gt = torch.full((Nc,), float('-inf'), device=dev, dtype=torch.float32)
-    for r0 in range(0, Ni, rb):                      # pass 1: the band -> ground-truth score of every caption
-        r1 = min(Ni, r0 + rb)
-        c0, c1 = min(Nc, r0 * im_div), min(Nc, r1 * im_div)
-        if c1 > c0:
-            band = score_fn(img[r0:r1], cap[c0:c1], out=buf[:(r1 - r0) * (c1 - c0)].view(r1 - r0, c1 - c0))
-            ops.gather_gt(band, im_div, 0, s_gt[c0:c1])
+    s_gt = _stream_band_gt(img, cap, score_fn, im_div, rb, buf)          # pass 1: the band -> ground-truth score of every caption
     t_rank = torch.zeros(Nc, device=dev, dtype=torch.int32)
     t_best = torch.zeros(Nc, device=dev, dtype=torch.int64)
     i_rank, i_top = [], []
@@ -540,6 +553,66 @@ def score_rank_streamed(img, cap, score_fn, im_div=5, budget_bytes=64 << 20, row
         timers['scan_end'].record()
     both = torch.stack([torch.cat(i_rank), torch.cat(i_top)], 1).cpu().numpy() if i_rank else np.zeros((0, 2), np.int64)
     return both[:, 0].astype(np.int64), both[:, 1].astype(np.int64), t_rank.cpu().numpy().astype(np.int64), (t_best & 0xffffffff).cpu().numpy()
+
+
+def score_topk_streamed(img, cap, score_fn, k, im_div=5, ranks=True, rows=True, cols=True, budget_bytes=64 << 20, rows_per_block=None,
+                        timers=None, comm=None):
+    """One process, pooled scorers: the top-k lists (and the Recall ranks) of score_fn(img, cap) WITHOUT the similarity matrix in memory
+    -- the coarse stage of coarse-to-fine retrieval for a gallery whose matrix does not fit (coco_precomp train: 113 287 x 566 435
+    is 257 GB of scores from under 3 GB of embeddings).  The block loop is score_rank_streamed's: with ranks=True the same first pass
+    over the diagonal band gives the ground-truth scores; then every row block is scored ONCE into the reused buffer and, while it is
+    still in the cache, ranked (ops.rank_counts), its row lists selected (ops.topk_lists: complete, a block spans every column) and
+    its columns folded into the running column lists (ops.topk_fold_cols, csrc/topk_fold.hip).  The lists are those of the whole
+    matrix for every block height (one total order on (score, index) keys; tests/test_score_topk_streamed_gpu.py).
+    rows / cols: either direction can be left out (a caption-to-image search needs no row pass); its two arrays are None then.
+    One process only: `comm` exists to say so -- a live (or virtual) Comm is refused with NotImplementedError, None or an idle one is fine.
+    -> (i2t_idx int64 [Ni, k], i2t_val [Ni, k], t2i_idx int64 [Nc, k], t2i_val [Nc, k]) as finalize_topk returns them, and with
+    ranks=True a second value, the tuple finalize_ranks returns."""
+    if comm is not None and (comm.on or comm.virtual):
+        raise NotImplementedError("score_topk_streamed: one process only (the streamed coarse stage has no multi-GPU form)")
+    Ni, Nc = img.shape[0], cap.shape[0]
+    dev = img.device
+    k = int(k)
+    rb = _stream_rows_per_block(Nc, budget_bytes, rows_per_block)
+    if timers is not None:
+        timers['scan_start'].record()
+    buf = torch.empty(min(rb, Ni) * Nc, device=dev, dtype=torch.float32)
+    s_gt = t_rank = t_best = None
+    if ranks:
+        s_gt = _stream_band_gt(img, cap, score_fn, im_div, rb, buf)      # pass 1: the band -> ground-truth score of every caption
+        t_rank = torch.zeros(Nc, device=dev, dtype=torch.int32)
+        t_best = torch.zeros(Nc, device=dev, dtype=torch.int64)
+    i_rank, i_top, r_idx, r_val = [], [], [], []
+    state = None
+    if cols:
+        state = (torch.zeros(Nc, k, device=dev, dtype=torch.int64), torch.zeros(Nc, k, device=dev, dtype=torch.float32))
+    for r0 in range(0, Ni, rb):                      # pass 2: a row block of scores, consumed while it is still in the cache
+        r1 = min(Ni, r0 + rb)
+        blk = score_fn(img[r0:r1], cap, out=buf[:(r1 - r0) * Nc].view(r1 - r0, Nc))
+        if ranks:
+            ir, it, _, _, _ = ops.rank_counts(blk, im_div, r0, s_gt, t_rank, t_best)
+            i_rank.append(ir)
+            i_top.append(it)
+        if rows:
+            ri, rv, _ = ops.topk_lists(blk, k, r0, rows=True, cols=False)
+            r_idx.append(ri)
+            r_val.append(rv)
+        if cols:
+            ops.topk_fold_cols(blk, k, r0, state)
+    if timers is not None:
+        timers['scan_end'].record()
+    lists = [None, None, None, None]
+    if rows:
+        lists[0] = (torch.cat(r_idx) if r_idx else torch.zeros(0, k, dtype=torch.int32)).cpu().numpy().astype(np.int64)
+        lists[1] = (torch.cat(r_val) if r_val else torch.zeros(0, k)).cpu().numpy()
+    if cols:
+        c_idx, c_val = ops.topk_merge_cols([state], k)
+        lists[2], lists[3] = c_idx.cpu().numpy().astype(np.int64), c_val.cpu().numpy()
+    if not ranks:
+        return tuple(lists)
+    both = torch.stack([torch.cat(i_rank), torch.cat(i_top)], 1).cpu().numpy() if i_rank else np.zeros((0, 2), np.int64)
+    return tuple(lists), (both[:, 0].astype(np.int64), both[:, 1].astype(np.int64), t_rank.cpu().numpy().astype(np.int64),
+                          (t_best & 0xffffffff).cpu().numpy())
 
 
 class PooledModelEval:

@@ -427,24 +427,102 @@ def rerank(sims_coarse, score_fn, k, im_div=5):
     for lists of image indices per caption) returns their fine scores [n, k], and ops.rerank_lists re-orders them.
     -> ((r1, r5, r10, medr, meanr) i2t, the same for t2i, (i2t_ranks, t2i_ranks), lists) with lists = {'i2t_topk', 'i2t_topk_scores',
     't2i_topk', 't2i_topk_scores'} (the reranked lists and their fine scores) as `topk` lays them out."""
-    k = int(k)
-    if k < 10:
-        raise ValueError("rerank: k = %d < 10: R@10 would not be defined by the shortlist" % k)
+    k = _rerank_args("rerank", k)
     S = _device_matrix(sims_coarse)
     if S.dtype != torch.float32:
         S = S.to(torch.float32)
     r_idx, _, part = ops.topk_lists(S, k)
     c_idx, _ = ops.topk_merge_cols([part], k)
     i_rank, _, t_rank, _, _ = ops.rank_counts(S, im_div)
-    fine_i = score_fn(r_idx, 'image')
-    fine_t = score_fn(c_idx, 'caption')
-    ri, rv, _ = ops.rerank_lists(r_idx, fine_i)
-    ci, cv, _ = ops.rerank_lists(c_idx, fine_t)
-    lists = {'i2t_topk': ri.cpu().numpy().astype(np.int64), 'i2t_topk_scores': rv.cpu().numpy(),
-             't2i_topk': ci.cpu().numpy().astype(np.int64), 't2i_topk_scores': cv.cpu().numpy()}
-    i_ranks = rerank_rank_vector(lists['i2t_topk'], i_rank.cpu().numpy(), 'i2t', im_div)
-    t_ranks = rerank_rank_vector(lists['t2i_topk'], t_rank.cpu().numpy(), 't2i', im_div)
+    return _rerank_tail(r_idx, c_idx, i_rank.cpu().numpy(), t_rank.cpu().numpy(), score_fn, None, im_div)
+
+
+def _rerank_args(who, k, score_fns=None):
+    """The argument rules of rerank / rerank_ensemble and their streamed forms -> int(k)."""
+    k = int(k)
+    if k < 10:
+        raise ValueError("%s: k = %d < 10: R@10 would not be defined by the shortlist" % (who, k))
+    if score_fns is not None and not 1 <= len(score_fns) <= 4:
+        raise ValueError("%s: 1 to 4 fine members, got %d" % (who, len(score_fns)))
+    return k
+
+
+def _rerank_tail(r_idx, c_idx, i_rank, t_rank, score_fn, score_fns, im_div):
+    """What follows the coarse stage, whichever way it produced the shortlists (r_idx / c_idx int32 device [n, k]) and the coarse
+    ranks (host [n]): fine scores, ops.rerank_lists (score_fn) or ops.rerank_fused_lists (score_fns, the ensemble), the reranked
+    rank vectors.  -> `rerank`'s / `rerank_ensemble`'s tuple.  The materialised and the streamed forms both end here."""
+    if score_fns is None:
+        fine_i = score_fn(r_idx, 'image')
+        fine_t = score_fn(c_idx, 'caption')
+        ri, rv, _ = ops.rerank_lists(r_idx, fine_i)
+        ci, cv, _ = ops.rerank_lists(c_idx, fine_t)
+        lists = {'i2t_topk': ri.cpu().numpy().astype(np.int64), 'i2t_topk_scores': rv.cpu().numpy(),
+                 't2i_topk': ci.cpu().numpy().astype(np.int64), 't2i_topk_scores': cv.cpu().numpy()}
+    else:
+        fine_i, fine_t = [], []
+        for f in score_fns:
+            fn = f() if _is_factory(f) else f
+            fine_i.append(fn(r_idx, 'image'))
+            fine_t.append(fn(c_idx, 'caption'))
+            del fn                                # a factory's state goes before the next member's is built
+        ri, rf, rv, _ = ops.rerank_fused_lists(r_idx, fine_i)
+        ci, cf, cv, _ = ops.rerank_fused_lists(c_idx, fine_t)
+        lists = {'i2t_topk': ri.cpu().numpy().astype(np.int64), 'i2t_topk_scores': rf.cpu().numpy(),
+                 'i2t_topk_member_scores': rv.cpu().numpy(),
+                 't2i_topk': ci.cpu().numpy().astype(np.int64), 't2i_topk_scores': cf.cpu().numpy(),
+                 't2i_topk_member_scores': cv.cpu().numpy()}
+    i_ranks = rerank_rank_vector(lists['i2t_topk'], i_rank, 'i2t', im_div)
+    t_ranks = rerank_rank_vector(lists['t2i_topk'], t_rank, 't2i', im_div)
     return ops.recall_from_ranks(i_ranks), ops.recall_from_ranks(t_ranks), (i_ranks, t_ranks), lists
+
+
+def _streamed_coarse(img_emb, cap_emb, coarse_score_fn, k, im_div):
+    """The coarse stage of `rerank_streamed` / `rerank_ensemble_streamed`: evalpipe.score_topk_streamed -> the shortlists back on
+    the device (int32, what the fine scorers take) and the streamed coarse rank tuple."""
+    from .. import evalpipe
+    dev = torch.device('cuda', torch.cuda.current_device())
+    img = img_emb if torch.is_tensor(img_emb) else torch.from_numpy(np.ascontiguousarray(img_emb))
+    cap = cap_emb if torch.is_tensor(cap_emb) else torch.from_numpy(np.ascontiguousarray(cap_emb))
+    (i_idx, _, t_idx, _), ranks = evalpipe.score_topk_streamed(img.to(dev), cap.to(dev), coarse_score_fn, k, im_div)
+    r_idx = torch.from_numpy(i_idx.astype(np.int32)).to(dev)
+    c_idx = torch.from_numpy(t_idx.astype(np.int32)).to(dev)
+    return r_idx, c_idx, ranks
+
+
+def rerank_streamed(img_emb, cap_emb, coarse_score_fn, score_fn, k, im_div=5, return_coarse_ranks=False):
+    """`rerank` for a gallery whose coarse matrix does not fit: the shortlists and the coarse ranks come from
+    evalpipe.score_topk_streamed(img_emb, cap_emb, coarse_score_fn, k) -- the matrix is scored in cache-sized row blocks and never
+    stored, neither on the device nor on the host -- and everything after the coarse stage is `rerank`'s own code (_rerank_tail).
+    coarse_score_fn(img_rows, cap, out=) is a pooled scorer (ops.cosine_scores, ops.order_scores, ops.pdist_cos, ops.mvm_scores).
+    -> `rerank`'s tuple, entry for entry that of rerank(coarse_score_fn(img_emb, cap_emb), score_fn, k); with
+    return_coarse_ranks=True also the streamed coarse rank tuple (i2t_rank, i2t_top1, t2i_rank, t2i_top1)."""
+    k = _rerank_args("rerank_streamed", k)
+    r_idx, c_idx, ranks = _streamed_coarse(img_emb, cap_emb, coarse_score_fn, k, im_div)
+    out = _rerank_tail(r_idx, c_idx, ranks[0], ranks[2], score_fn, None, im_div)
+    return (out, ranks) if return_coarse_ranks else out
+
+
+def rerank_ensemble_streamed(img_emb, cap_emb, coarse_score_fn, score_fns, k, im_div=5, return_coarse_ranks=False):
+    """`rerank_ensemble` with `rerank_streamed`'s coarse stage (the coarse matrix is never stored).  -> `rerank_ensemble`'s tuple."""
+    score_fns = list(score_fns)
+    k = _rerank_args("rerank_ensemble_streamed", k, score_fns)
+    r_idx, c_idx, ranks = _streamed_coarse(img_emb, cap_emb, coarse_score_fn, k, im_div)
+    out = _rerank_tail(r_idx, c_idx, ranks[0], ranks[2], None, score_fns, im_div)
+    return (out, ranks) if return_coarse_ranks else out
+
+
+def _streamed_coarse_scorer(name, cfg, who):
+    """The pooled op cal_sims reaches for a coarse family (evalpipe.PooledModelEval._score has the same mapping), in its out= form."""
+    if name in ('SCAN', 'SGRAF'):
+        raise NotImplementedError("%s: stream_coarse needs a pooled coarse model (one vector per caption); the dense scorer of %s is not "
+                                  "streamed" % (who, name))
+    if name == 'CAMERA':
+        return ops.mvm_scores
+    if name == 'SAEM':
+        if cfg.get('measure') == 'order':
+            raise NotImplementedError("%s: stream_coarse has no streamed form of SAEM's euclidean pdist (measure = order)" % who)
+        return ops.pdist_cos
+    return ops.order_scores if cfg.get('measure') == 'order' else ops.cosine_scores
 
 
 def explain(lists, score_fn, m):
@@ -563,14 +641,18 @@ def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
     return fn
 
 
-def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split='dev', fold5=False, explain=None, explain_sgraf=None):
+def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split='dev', fold5=False, explain=None, explain_sgraf=None,
+                    stream_coarse=False):
     """Coarse-to-fine evaluation: the coarse model (any family evalrank_single scores) shortlists k candidates per query in both
     directions, the fine model -- SCAN (either cross_attn) or SGRAF (SAF or SGR) -- scores only those pairs, Recall@K is that of the reranked ranking
     (`rerank`).  Writes `<data_name>[_5fold]_rerank<k>_result.yaml` (the coarse-only numbers under 'coarse', the reranked ones
     under 'rerank') and the reranked lists `<data_name>[_5fold]_rerank<k>.npz` next to the coarse checkpoint.
     explain=M (1 <= M <= k, SCAN fine model, not with fold5): after re-ordering, the best M results of every query in both
     directions are explained (`explain`) and written to `<data_name>_rerank<k>_explain<M>.npz` next to the other files.
-    explain_sgraf=M (the same rules, SGRAF fine model): `explain_sgraf`'s arrays go to `<data_name>_rerank<k>_explain<M>_sgraf.npz`."""
+    explain_sgraf=M (the same rules, SGRAF fine model): `explain_sgraf`'s arrays go to `<data_name>_rerank<k>_explain<M>_sgraf.npz`.
+    stream_coarse=True (pooled coarse models: VSE++ cosine / order, SAEM cosine, CAMERA; SCAN / SGRAF -> NotImplementedError): the
+    coarse embeddings go to the device once and the coarse stage is `rerank_streamed`'s -- neither the fp32 nor the float64 coarse
+    matrix is ever built; the 'coarse' block comes from the streamed ranks.  Same files, same keys."""
     import os
     import yaml
     from ..datamodule import data_loader as data
@@ -600,6 +682,7 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
         raise NotImplementedError("evalrank_rerank: explain_sgraf needs an SGRAF fine model (a SCAN model explains itself through explain), got %s"
                                   % f_cfg['name'])
     fine_score_fn = _scan_score_fn if f_cfg['name'] == 'SCAN' else _sgraf_score_fn
+    coarse_fn = _streamed_coarse_scorer(c_cfg['name'], c_cfg, "evalrank_rerank") if stream_coarse else None
     if f_cfg['data_name'] != c_cfg['data_name']:
         raise ValueError("evalrank_rerank: the checkpoints name different datasets (%s, %s): their lists would not index the same items"
                          % (c_cfg['data_name'], f_cfg['data_name']))
@@ -613,11 +696,22 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
                          % (len(c_img), len(f_img), len(c_cap), len(f_cap)))
     lists, explained, reasoned = {}, {}, {}
 
+    if stream_coarse:                          # the coarse embeddings go to the device once; blocks below are views of them
+        dev = torch.device('cuda', torch.cuda.current_device())
+        c_img_dev = torch.from_numpy(np.ascontiguousarray(c_img)).to(dev)
+        c_cap_dev = torch.from_numpy(np.ascontiguousarray(c_cap)).to(dev)
+
     def block(sl_img, sl_cap, prefix):
-        sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
-        res_c = cal_recall(sims)
-        fn = fine_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
-        r, ri, (i_ranks, t_ranks), tl = rerank(sims.astype(np.float32), fn, k)
+        if stream_coarse:
+            fn = fine_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
+            (r, ri, (i_ranks, t_ranks), tl), c_ranks = rerank_streamed(c_img_dev[sl_img].contiguous(), c_cap_dev[sl_cap], coarse_fn, fn, k,
+                                                                       return_coarse_ranks=True)
+            res_c = _recall_dict(c_ranks)
+        else:
+            sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
+            res_c = cal_recall(sims)
+            fn = fine_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
+            r, ri, (i_ranks, t_ranks), tl = rerank(sims.astype(np.float32), fn, k)
         lists.update({prefix + key: v for key, v in tl.items()})
         if explain_m is not None:
             explained.update(_explain_lists(tl, fn, explain_m))
@@ -676,37 +770,19 @@ def rerank_ensemble(sims_coarse, score_fns, k, im_div=5):
     device state is then built, used for both directions and released before the next member's is built.
     -> `rerank`'s tuple; in lists, 'i2t_topk_scores' / 't2i_topk_scores' are the float64 fused scores and 'i2t_topk_member_scores'
     / 't2i_topk_member_scores' (float32 [M, n, k]) what each member gave the entries, in the reranked order."""
-    k = int(k)
-    if k < 10:
-        raise ValueError("rerank_ensemble: k = %d < 10: R@10 would not be defined by the shortlist" % k)
     score_fns = list(score_fns)
-    if not 1 <= len(score_fns) <= 4:
-        raise ValueError("rerank_ensemble: 1 to 4 fine members, got %d" % len(score_fns))
+    k = _rerank_args("rerank_ensemble", k, score_fns)
     S = _device_matrix(sims_coarse)
     if S.dtype != torch.float32:
         S = S.to(torch.float32)
     r_idx, _, part = ops.topk_lists(S, k)
     c_idx, _ = ops.topk_merge_cols([part], k)
     i_rank, _, t_rank, _, _ = ops.rank_counts(S, im_div)
-    fine_i, fine_t = [], []
-    for f in score_fns:
-        fn = f() if _is_factory(f) else f
-        fine_i.append(fn(r_idx, 'image'))
-        fine_t.append(fn(c_idx, 'caption'))
-        del fn                                # a factory's state goes before the next member's is built
-    ri, rf, rv, _ = ops.rerank_fused_lists(r_idx, fine_i)
-    ci, cf, cv, _ = ops.rerank_fused_lists(c_idx, fine_t)
-    lists = {'i2t_topk': ri.cpu().numpy().astype(np.int64), 'i2t_topk_scores': rf.cpu().numpy(),
-             'i2t_topk_member_scores': rv.cpu().numpy(),
-             't2i_topk': ci.cpu().numpy().astype(np.int64), 't2i_topk_scores': cf.cpu().numpy(),
-             't2i_topk_member_scores': cv.cpu().numpy()}
-    i_ranks = rerank_rank_vector(lists['i2t_topk'], i_rank.cpu().numpy(), 'i2t', im_div)
-    t_ranks = rerank_rank_vector(lists['t2i_topk'], t_rank.cpu().numpy(), 't2i', im_div)
-    return ops.recall_from_ranks(i_ranks), ops.recall_from_ranks(t_ranks), (i_ranks, t_ranks), lists
+    return _rerank_tail(r_idx, c_idx, i_rank.cpu().numpy(), t_rank.cpu().numpy(), None, score_fns, im_div)
 
 
 def evalrank_rerank_ensemble(model_path_coarse, model_paths_fine, k, data_path=None, split='dev', fold5=False, explain=None,
-                             explain_sgraf=None):
+                             explain_sgraf=None, stream_coarse=False):
     """`evalrank_rerank` with an ensemble of 1 to 4 fine checkpoints, each SCAN (either cross_attn) or SGRAF (SAF or SGR), in any
     mix: the coarse model shortlists k candidates per query in both directions, every fine model scores those pairs, the lists are
     re-ordered by the float64 mean of the members' scores (`rerank_ensemble`; SAF + SGR is the published SGRAF, SCAN t2i + i2t the
@@ -716,7 +792,8 @@ def evalrank_rerank_ensemble(model_path_coarse, model_paths_fine, k, data_path=N
     are not touched.
     explain=M / explain_sgraf=M (1 <= M <= k, not with fold5): the fused best M results of every query are explained by every SCAN /
     every SGRAF member (`explain` / `explain_sgraf` on the fused lists, one member at a time), member j (1-based position among
-    the fine checkpoints) in `<data_name>_rerank<k>_ensemble_explain<M>_member<j>.npz` / `..._member<j>_sgraf.npz`."""
+    the fine checkpoints) in `<data_name>_rerank<k>_ensemble_explain<M>_member<j>.npz` / `..._member<j>_sgraf.npz`.
+    stream_coarse=True: as in `evalrank_rerank` -- the coarse matrix is never built (`rerank_ensemble_streamed`)."""
     import os
     import yaml
     from ..datamodule import data_loader as data
@@ -742,6 +819,7 @@ def evalrank_rerank_ensemble(model_path_coarse, model_paths_fine, k, data_path=N
             raise NotImplementedError("evalrank_rerank_ensemble: every fine model must be SCAN or SGRAF (candidate-list scoring exists for "
                                       "these only), got %s" % f_cfg['name'])
     families = [f_cfg['name'] for _, f_cfg in fines]
+    coarse_fn = _streamed_coarse_scorer(c_cfg['name'], c_cfg, "evalrank_rerank_ensemble") if stream_coarse else None
     if 'explain' in wanted and 'SCAN' not in families:
         raise NotImplementedError("evalrank_rerank_ensemble: explain needs a SCAN member (attention maps exist for SCAN only; SGRAF members "
                                   "explain themselves through explain_sgraf), got %s" % ', '.join(families))
@@ -764,16 +842,25 @@ def evalrank_rerank_ensemble(model_path_coarse, model_paths_fine, k, data_path=N
     lists = {}
     explained = {}             # file suffix -> arrays
 
-    def block(sl_img, sl_cap, prefix):
-        sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
-        res_c = cal_recall(sims)
+    if stream_coarse:
+        dev = torch.device('cuda', torch.cuda.current_device())
+        c_img_dev = torch.from_numpy(np.ascontiguousarray(c_img)).to(dev)
+        c_cap_dev = torch.from_numpy(np.ascontiguousarray(c_cap)).to(dev)
 
+    def block(sl_img, sl_cap, prefix):
         def factory(j):
             make = _scan_score_fn if families[j] == 'SCAN' else _sgraf_score_fn
             f_img, f_cap, f_len = f_embs[j]
             return lambda: make(fines[j][0], f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
         factories = [factory(j) for j in range(len(fines))]
-        r, ri, (i_ranks, t_ranks), tl = rerank_ensemble(sims.astype(np.float32), factories, k)
+        if stream_coarse:
+            (r, ri, (i_ranks, t_ranks), tl), c_ranks = rerank_ensemble_streamed(c_img_dev[sl_img].contiguous(), c_cap_dev[sl_cap], coarse_fn,
+                                                                                factories, k, return_coarse_ranks=True)
+            res_c = _recall_dict(c_ranks)
+        else:
+            sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
+            res_c = cal_recall(sims)
+            r, ri, (i_ranks, t_ranks), tl = rerank_ensemble(sims.astype(np.float32), factories, k)
         lists.update({prefix + key: v for key, v in tl.items()})
         for j, family in enumerate(families):          # one member's state at a time, rebuilt for the explanation
             if family == 'SCAN' and 'explain' in wanted:

@@ -1129,6 +1129,44 @@ def topk_merge_cols(parts, k):
     return col_idx, col_val
 
 
+def topk_fold_cols(S_block, k, row0=0, state=None):
+    """Fold ONE row block of a similarity matrix that is never stored into running column lists (csrc/topk_fold.hip).
+    S_block: fp32 [n, Nc] holding global rows row0 .. row0 + n - 1; tensor rules of `topk_lists` (GPU only, a row-strided view is
+    taken as it is).  state: (key int64 [Nc, k], val float32 [Nc, k]) in the layout of `topk_lists`' column part -- None starts
+    from empty lists (zeros), a part of `topk_lists` (same k) is a valid state; a given state is updated IN PLACE and returned.
+    After the call the lists hold the k largest keys of (the lists before) U (this block's columns): every partition of a matrix
+    into row blocks, folded in any order, gives bit for bit the lists of the whole matrix.  The block's rows must not be in the
+    lists already (not checked).  `topk_merge_cols([state], k)` is the finishing step -> (col_idx, col_val)."""
+    lib = _lib.load()
+    if not torch.is_tensor(S_block):
+        raise TypeError("S_block must be a torch tensor")
+    if S_block.dim() != 2:
+        raise ValueError("topk_fold_cols: S_block must be 2-D, got shape %s" % (tuple(S_block.shape),))
+    S_ = _dev_view(S_block, torch.float32)
+    n, Nc = S_.shape
+    dev = S_.device
+    k = int(k)
+    if k < 1 or k > TOPK_MAX:
+        raise NotImplementedError("topk_fold_cols: k = %d outside 1 .. ITR_TOPK_MAX = %d" % (k, TOPK_MAX))
+    if state is None:
+        state = (torch.zeros(Nc, k, device=dev, dtype=torch.int64), torch.zeros(Nc, k, device=dev, dtype=torch.float32))
+    else:
+        if not (isinstance(state, (tuple, list)) and len(state) == 2 and all(torch.is_tensor(t) for t in state)):
+            raise ValueError("topk_fold_cols: state must be (key int64 [Nc, k], val float32 [Nc, k])")
+        key, val = state
+        for t, dt, nm in ((key, torch.int64, "key"), (val, torch.float32, "val")):
+            if tuple(t.shape) != (Nc, k) or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError("topk_fold_cols: state %s must be a contiguous %s tensor of shape (%d, %d) on %s, got %s %s on %s"
+                                 % (nm, dt, Nc, k, dev, t.dtype, tuple(t.shape), t.device))
+        state = (key, val)
+    if n == 0 or Nc == 0:                  # nothing to fold (an empty tensor has no address to hand to the library)
+        return state
+    wsb = lib.itr_topk_fold_workspace_bytes(n, Nc, k)
+    ws = torch.empty(wsb // 8 + 1, device=dev, dtype=torch.int64) if wsb else None
+    _lib.check(lib.itr_topk_fold_cols(_p(S_), S_.stride(0), int(row0), n, Nc, k, _p(state[0]), _p(state[1]), _p(ws), wsb, _stream()))
+    return state
+
+
 # ------------------------------------------------------------------------------------------ candidate lists (coarse-to-fine retrieval)
 def _pairs_state(plan, dev):
     """Device copies of ALL captions' offsets and lengths for the pair kernel (a ScanPlan keeps only those of the captions its

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Evaluate checkpoints like the reference's test.py:  python test.py MODEL_PATH [MODEL_PATH_2] [--data-path P]
-[--split test|testall|dev] [--fold5] [--topk K] [--rerank K [--explain M | --explain-sgraf M]]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
+[--split test|testall|dev] [--fold5] [--topk K] [--rerank K [--stream-coarse] [--explain M | --explain-sgraf M]]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
 (and with --topk K the top-K retrieval lists of every query in <data_name>[_5fold]_{single,ensemble}_top<K>.npz).
 python test.py COARSE_PATH FINE_PATH --rerank K: coarse-to-fine retrieval, the first model shortlists K candidates per query and the
 second (SCAN or SGRAF) scores only those  ->  <data_name>[_5fold]_rerank<K>_result.yaml and <data_name>[_5fold]_rerank<K>.npz
@@ -38,7 +38,12 @@ if __name__ == "__main__":
     ap.add_argument("--explain-sgraf", type=int, default=None, metavar="M",
                     help="with --rerank K and an SGRAF fine model: also write the attention, filtration weights (SAF) or graph edges (SGR) "
                          "of the best M <= K results of every query")
+    ap.add_argument("--stream-coarse", action="store_true",
+                    help="with --rerank K and a pooled coarse model: the coarse similarity matrix is streamed in row blocks and never "
+                         "stored (a gallery whose matrix does not fit); same files")
     a = ap.parse_args()
+    if a.stream_coarse and not a.rerank:
+        ap.error("--stream-coarse needs --rerank K")
     if a.explain is not None and not a.rerank:
         ap.error("--explain needs --rerank K")
     if a.explain_sgraf is not None and not a.rerank:
@@ -50,10 +55,10 @@ if __name__ == "__main__":
             ap.error("--rerank does not combine with --fast or --topk (the reranked lists are written to ..._rerank<K>.npz)")
         if len(a.model_path) == 2:
             evaluation.evalrank_rerank(a.model_path[0], a.model_path[1], a.rerank, data_path=a.data_path, split=a.split, fold5=a.fold5,
-                                       explain=a.explain, explain_sgraf=a.explain_sgraf)
+                                       explain=a.explain, explain_sgraf=a.explain_sgraf, stream_coarse=a.stream_coarse)
         else:
             evaluation.evalrank_rerank_ensemble(a.model_path[0], a.model_path[1:], a.rerank, data_path=a.data_path, split=a.split,
-                                                fold5=a.fold5, explain=a.explain, explain_sgraf=a.explain_sgraf)
+                                                fold5=a.fold5, explain=a.explain, explain_sgraf=a.explain_sgraf, stream_coarse=a.stream_coarse)
     elif a.fast:
         import torch
         import torch.distributed as dist

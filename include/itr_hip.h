@@ -397,6 +397,27 @@ int itr_topk_merge(const uint64_t *part_key, const float *part_val, int n_parts,
 int itr_topk_f64(const double *S, int64_t ldS, int64_t n_rows, int64_t Nc, int K, int32_t *row_idx, double *row_val,
                  int32_t *col_idx, double *col_val, itr_stream_t stream);
 
+/* ---- running top-K column lists: a similarity matrix that is never stored (csrc/topk_fold.hip) ----
+ * itr_topk_fold_cols folds ONE row block S [n_rows_local, Nc] (global rows row0 .. row0 + n_rows_local - 1, leading dimension
+ * ldS >= Nc, any alignment) into running column lists col_key [Nc, K] / col_val [Nc, K], which the call reads AND writes.  Their
+ * layout is exactly that of itr_topk's column part: keys = ordered score << 32 | GLOBAL row, best first, key 0 = empty entry;
+ * col_val holds the ORIGINAL bits of the score (carried along with its key, never rebuilt from it: a -0.0 stays -0.0, a NaN
+ * stays NaN).  After the call the lists hold the K largest keys of (the lists before) U (the entries of this block's columns).
+ *   - All zeros is the empty starting state; a part written by itr_topk (same K) is a valid starting state too.
+ *   - A state is a valid part for itr_topk_merge: itr_topk_merge(state, 1 part, K_in = K) turns it into col_idx / col_val.
+ *   - The result is a function of the SET of keys alone: any partition of a matrix into row blocks, folded in any order, gives
+ *     bit for bit the whole-matrix lists of itr_topk + itr_topk_merge, however the workgroups of a call are scheduled.
+ *   - PRECONDITION (documented, not checked): the block's rows are not in the lists already (a row folded twice is listed twice).
+ *   - No host read-back and no allocation inside the call.  workspace: itr_topk_fold_workspace_bytes(n_rows_local, Nc, K) bytes
+ *     (currently 0 for every shape: a strip of columns is merged where it lies; NULL is accepted then).
+ * Arguments as for itr_topk, except that K outside 1 .. ITR_TOPK_MAX is ITR_ERR_UNSUPPORTED on either side; null S or outputs,
+ * ldS < Nc, negative sizes, rows beyond the key's 32-bit index -> ITR_ERR_BADARG; n_rows_local == 0 or Nc == 0 -> ITR_OK,
+ * nothing written.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+size_t itr_topk_fold_workspace_bytes(int64_t n_rows_local, int64_t Nc, int K);
+int itr_topk_fold_cols(const float *S, int64_t ldS, int64_t row0, int64_t n_rows_local, int64_t Nc, int K,
+                       uint64_t *col_key, float *col_val, void *workspace, size_t workspace_bytes, itr_stream_t stream);
+
 /* ---- a6 on candidate lists: xattn_score_t2i / xattn_score_i2t (Objectives.py:329-476) for LISTED (image, caption) pairs ----
  * The fine stage of coarse-to-fine retrieval: only the P listed pairs are scored (csrc/scan_pairs.hip), with the arithmetic of
  * itr_scan_xattn_scores (exact fp32 dot products, Gram-form cosine; same mode / norm / agg codes, lambda_softmax, lambda_lse).
