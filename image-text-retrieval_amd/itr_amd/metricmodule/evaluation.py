@@ -428,13 +428,8 @@ def rerank(sims_coarse, score_fn, k, im_div=5):
     -> ((r1, r5, r10, medr, meanr) i2t, the same for t2i, (i2t_ranks, t2i_ranks), lists) with lists = {'i2t_topk', 'i2t_topk_scores',
     't2i_topk', 't2i_topk_scores'} (the reranked lists and their fine scores) as `topk` lays them out."""
     k = _rerank_args("rerank", k)
-    S = _device_matrix(sims_coarse)
-    if S.dtype != torch.float32:
-        S = S.to(torch.float32)
-    r_idx, _, part = ops.topk_lists(S, k)
-    c_idx, _ = ops.topk_merge_cols([part], k)
-    i_rank, _, t_rank, _, _ = ops.rank_counts(S, im_div)
-    return _rerank_tail(r_idx, c_idx, i_rank.cpu().numpy(), t_rank.cpu().numpy(), score_fn, None, im_div)
+    r_idx, c_idx, i_rank, t_rank = _materialised_coarse(sims_coarse, k, im_div)
+    return _rerank_tail(r_idx, c_idx, i_rank, t_rank, score_fn, None, im_div)
 
 
 def _rerank_args(who, k, score_fns=None):
@@ -474,6 +469,18 @@ def _rerank_tail(r_idx, c_idx, i_rank, t_rank, score_fn, score_fns, im_div):
     i_ranks = rerank_rank_vector(lists['i2t_topk'], i_rank, 'i2t', im_div)
     t_ranks = rerank_rank_vector(lists['t2i_topk'], t_rank, 't2i', im_div)
     return ops.recall_from_ranks(i_ranks), ops.recall_from_ranks(t_ranks), (i_ranks, t_ranks), lists
+
+
+def _materialised_coarse(sims_coarse, k, im_div):
+    """The coarse stage of `rerank` / `rerank_ensemble` on a stored matrix: the k-lists of both directions from the top-k path
+    (int32, on the device) and the coarse rank vectors (host) -> (r_idx, c_idx, i_rank, t_rank)."""
+    S = _device_matrix(sims_coarse)
+    if S.dtype != torch.float32:
+        S = S.to(torch.float32)
+    r_idx, _, part = ops.topk_lists(S, k)
+    c_idx, _ = ops.topk_merge_cols([part], k)
+    i_rank, _, t_rank, _, _ = ops.rank_counts(S, im_div)
+    return r_idx, c_idx, i_rank.cpu().numpy(), t_rank.cpu().numpy()
 
 
 def _streamed_coarse(img_emb, cap_emb, coarse_score_fn, k, im_div):
@@ -535,20 +542,26 @@ def explain(lists, score_fn, m):
     attention = getattr(score_fn, 'attention', None)
     if attention is None:
         raise NotImplementedError("explain: attention maps exist for a SCAN fine model only (an SGRAF scorer explains itself through explain_sgraf)")
+    return _explain_both("explain", lists, attention, m, lambda a: ('row_sim', 'row_ptr', 'cap_len'))
+
+
+def _explain_both(who, lists, explainer, m, own):
+    """The two directions of `explain` / `explain_sgraf`: the first m columns of each direction's lists go to the device,
+    explainer(cand, by, m) -> ops.ScanPairAttention / ops.SgrafPairAttention `a`, and its arrays come back under 'i2t_' / 't2i_':
+    idx, scores, attn, attn_ptr, then the attributes own(a) names."""
     m = int(m)
     out = {}
     for d, by in (('i2t', 'image'), ('t2i', 'caption')):
         idx = np.asarray(lists[d + '_topk'])
         if m < 1 or m > idx.shape[1]:
-            raise ValueError("explain: m = %d outside [1, %d]" % (m, idx.shape[1]))
+            raise ValueError("%s: m = %d outside [1, %d]" % (who, m, idx.shape[1]))
         dev = torch.device('cuda', torch.cuda.current_device())
         cand = torch.from_numpy(np.ascontiguousarray(idx[:, :m]).astype(np.int32)).to(dev)
-        a = attention(cand, by, m)
+        a = explainer(cand, by, m)
         n = idx.shape[0]
         out.update({d + '_idx': idx[:, :m].astype(np.int64), d + '_scores': a.score.cpu().numpy().reshape(n, m),
-                    d + '_attn': a.attn.cpu().numpy(), d + '_attn_ptr': a.attn_ptr.cpu().numpy(),
-                    d + '_row_sim': a.row_sim.cpu().numpy(), d + '_row_ptr': a.row_ptr.cpu().numpy(),
-                    d + '_cap_len': a.cap_len.cpu().numpy()})
+                    d + '_attn': a.attn.cpu().numpy(), d + '_attn_ptr': a.attn_ptr.cpu().numpy()})
+        out.update({d + '_' + name: getattr(a, name).cpu().numpy() for name in own(a)})
     return out
 
 
@@ -566,24 +579,8 @@ def explain_sgraf(lists, score_fn, m):
     reasoning = getattr(score_fn, 'reasoning', None)
     if reasoning is None:
         raise NotImplementedError("explain_sgraf: reasoning maps exist for an SGRAF fine model only (SCAN: explain)")
-    m = int(m)
-    out = {}
-    for d, by in (('i2t', 'image'), ('t2i', 'caption')):
-        idx = np.asarray(lists[d + '_topk'])
-        if m < 1 or m > idx.shape[1]:
-            raise ValueError("explain_sgraf: m = %d outside [1, %d]" % (m, idx.shape[1]))
-        dev = torch.device('cuda', torch.cuda.current_device())
-        cand = torch.from_numpy(np.ascontiguousarray(idx[:, :m]).astype(np.int32)).to(dev)
-        a = reasoning(cand, by, m)
-        n = idx.shape[0]
-        out.update({d + '_idx': idx[:, :m].astype(np.int64), d + '_scores': a.score.cpu().numpy().reshape(n, m),
-                    d + '_attn': a.attn.cpu().numpy(), d + '_attn_ptr': a.attn_ptr.cpu().numpy(),
-                    d + '_cap_len': a.cap_len.cpu().numpy(), d + '_explained': a.explained.cpu().numpy()})
-        if a.node_w is not None:
-            out.update({d + '_node_w': a.node_w.cpu().numpy(), d + '_node_ptr': a.node_ptr.cpu().numpy()})
-        else:
-            out.update({d + '_edge': a.edge.cpu().numpy(), d + '_edge_ptr': a.edge_ptr.cpu().numpy()})
-    return out
+    return _explain_both("explain_sgraf", lists, reasoning, m,
+                         lambda a: ('cap_len', 'explained') + (('node_w', 'node_ptr') if a.node_w is not None else ('edge', 'edge_ptr')))
 
 
 _explain_sgraf_lists = explain_sgraf
@@ -622,15 +619,7 @@ def _scan_score_fn(model, img_embs, cap_embs, cap_lens):
     """score_fn of `rerank` for a SCAN model: its word-level caption embeddings packed once, the pair workspace prepared once.
     Its attribute `attention(cand, by, m)` is ops.scan_candidate_attention on the same operands and workspace (`explain`)."""
     cfg = model.config
-    dev = torch.device('cuda', torch.cuda.current_device())
-    lens = np.asarray(cap_lens, dtype=np.int64)
-    images = torch.from_numpy(np.ascontiguousarray(img_embs)).to(dev)
-    caps = torch.from_numpy(np.ascontiguousarray(cap_embs)).to(dev)
-    L = caps.shape[1]
-    keep = (torch.arange(L, device=dev)[None, :] < torch.from_numpy(lens).to(dev)[:, None]).reshape(-1)
-    words = caps.reshape(-1, caps.shape[2])[keep].contiguous()
-    off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-    plan = ops.ScanPlan(off, lens.astype(np.int32), words.shape[0], dev)
+    images, words, plan = _packed_words(img_embs, cap_embs, cap_lens)
     kw = dict(cross_attn=cfg['cross_attn'], raw_feature_norm=cfg['raw_feature_norm'], agg_func=cfg['agg_func'],
               lambda_lse=cfg['lambda_lse'], lambda_softmax=cfg['lambda_softmax'])
     ws = ops.scan_pairs_prepare(images, words, plan, cfg['cross_attn'])
@@ -653,48 +642,68 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
     stream_coarse=True (pooled coarse models: VSE++ cosine / order, SAEM cosine, CAMERA; SCAN / SGRAF -> NotImplementedError): the
     coarse embeddings go to the device once and the coarse stage is `rerank_streamed`'s -- neither the fp32 nor the float64 coarse
     matrix is ever built; the 'coarse' block comes from the streamed ranks.  Same files, same keys."""
+    return _evalrank_rerank("evalrank_rerank", False, model_path_coarse, [model_path_fine], k, data_path, split, fold5, explain, explain_sgraf,
+                            stream_coarse)
+
+
+def _evalrank_rerank(who, ensemble, model_path_coarse, model_paths_fine, k, data_path, split, fold5, explain, explain_sgraf, stream_coarse):
+    """The driver of `evalrank_rerank` (ensemble=False: one fine checkpoint, its float32 scores re-order the lists through `rerank`)
+    and `evalrank_rerank_ensemble` (ensemble=True: 1 to 4, fused in float64 through `rerank_ensemble`, also when there is one: the
+    two forms write different scores and files).  The forms differ in the fine stage of a block, the file stem, the YAML key of
+    the fine path(s), the printed lines and the explanation files' names; everything else is here once."""
     import os
     import yaml
     from ..datamodule import data_loader as data
-    if int(k) < 10:
-        raise ValueError("evalrank_rerank: k = %d < 10: R@10 would not be defined by the shortlist" % int(k))
-    explain_m = None if explain is None else int(explain)
-    if explain_m is not None:
+    k = int(k)
+    if k < 10:
+        raise ValueError("%s: k = %d < 10: R@10 would not be defined by the shortlist" % (who, k))
+    if ensemble and not 1 <= len(model_paths_fine) <= 4:
+        raise ValueError("%s: 1 to 4 fine checkpoints, got %d" % (who, len(model_paths_fine)))
+    one = 'member' if ensemble else 'fine model'
+    wanted = {}
+    for name, m in (('explain', explain), ('explain_sgraf', explain_sgraf)):
+        if m is None:
+            continue
         if fold5:
-            raise ValueError("evalrank_rerank: explain does not combine with fold5")
-        if explain_m < 1 or explain_m > int(k):
-            raise ValueError("evalrank_rerank: explain = %d outside [1, k = %d]" % (explain_m, int(k)))
-    sgraf_m = None if explain_sgraf is None else int(explain_sgraf)
-    if sgraf_m is not None:
-        if fold5:
-            raise ValueError("evalrank_rerank: explain_sgraf does not combine with fold5")
-        if sgraf_m < 1 or sgraf_m > int(k):
-            raise ValueError("evalrank_rerank: explain_sgraf = %d outside [1, k = %d]" % (sgraf_m, int(k)))
+            raise ValueError("%s: %s does not combine with fold5" % (who, name))
+        if int(m) < 1 or int(m) > k:
+            raise ValueError("%s: %s = %d outside [1, k = %d]" % (who, name, int(m), k))
+        wanted[name] = int(m)
     coarse, c_cfg = _load_for_eval(model_path_coarse, data_path)
-    fine, f_cfg = _load_for_eval(model_path_fine, data_path)
-    if f_cfg['name'] not in ('SCAN', 'SGRAF'):
-        raise NotImplementedError("evalrank_rerank: the fine model must be SCAN or SGRAF (candidate-list scoring exists for these only), got %s"
-                                  % f_cfg['name'])
-    if explain_m is not None and f_cfg['name'] != 'SCAN':
-        raise NotImplementedError("evalrank_rerank: explain needs a SCAN fine model (attention maps exist for SCAN only; an SGRAF model "
-                                  "explains itself through explain_sgraf), got %s" % f_cfg['name'])
-    if sgraf_m is not None and f_cfg['name'] != 'SGRAF':
-        raise NotImplementedError("evalrank_rerank: explain_sgraf needs an SGRAF fine model (a SCAN model explains itself through explain), got %s"
-                                  % f_cfg['name'])
-    fine_score_fn = _scan_score_fn if f_cfg['name'] == 'SCAN' else _sgraf_score_fn
-    coarse_fn = _streamed_coarse_scorer(c_cfg['name'], c_cfg, "evalrank_rerank") if stream_coarse else None
-    if f_cfg['data_name'] != c_cfg['data_name']:
-        raise ValueError("evalrank_rerank: the checkpoints name different datasets (%s, %s): their lists would not index the same items"
-                         % (c_cfg['data_name'], f_cfg['data_name']))
+    fines = [_load_for_eval(p, data_path) for p in model_paths_fine]
+    families = [f_cfg['name'] for _, f_cfg in fines]
+    for family in families:
+        if family not in ('SCAN', 'SGRAF'):
+            raise NotImplementedError("%s: %s fine model must be SCAN or SGRAF (candidate-list scoring exists for these only), got %s"
+                                      % (who, 'every' if ensemble else 'the', family))
+
+    def coarse_scorer():
+        return _streamed_coarse_scorer(c_cfg['name'], c_cfg, who) if stream_coarse else None
+    if ensemble:               # (the ensemble refuses an unstreamable coarse model before the explain rules, the single form after: kept)
+        coarse_fn = coarse_scorer()
+    if 'explain' in wanted and 'SCAN' not in families:
+        raise NotImplementedError("%s: explain needs a SCAN %s (attention maps exist for SCAN only; an SGRAF %s explains itself through "
+                                  "explain_sgraf), got %s" % (who, one, one, ', '.join(families)))
+    if 'explain_sgraf' in wanted and 'SGRAF' not in families:
+        raise NotImplementedError("%s: explain_sgraf needs an SGRAF %s (a SCAN %s explains itself through explain), got %s"
+                                  % (who, one, one, ', '.join(families)))
+    if not ensemble:
+        coarse_fn = coarse_scorer()
+    for _, f_cfg in fines:
+        if f_cfg['data_name'] != c_cfg['data_name']:
+            raise ValueError("%s: the checkpoints name different datasets (%s, %s): their lists would not index the same items"
+                             % (who, c_cfg['data_name'], f_cfg['data_name']))
     embs = []
-    for model, cfg in ((coarse, c_cfg), (fine, f_cfg)):
+    for model, cfg in [(coarse, c_cfg)] + fines:
         loader, _ = data.get_test_loader(split, cfg['data_name'], cfg['batch_size'], cfg['workers'], cfg)
         embs.append(encode_data(model, loader, islength=cfg['name'] in ['SGRAF', 'SCAN']))
-    (c_img, c_cap, c_len), (f_img, f_cap, f_len) = embs
-    if len(c_img) != len(f_img) or len(c_cap) != len(f_cap):
-        raise ValueError("evalrank_rerank: the two models' loaders hold different item counts (%d / %d images, %d / %d captions)"
-                         % (len(c_img), len(f_img), len(c_cap), len(f_cap)))
-    lists, explained, reasoned = {}, {}, {}
+    (c_img, c_cap, c_len), f_embs = embs[0], embs[1:]
+    for f_img, f_cap, _ in f_embs:
+        if len(c_img) != len(f_img) or len(c_cap) != len(f_cap):
+            raise ValueError("%s: the models' loaders hold different item counts (%d / %d images, %d / %d captions)"
+                             % (who, len(c_img), len(f_img), len(c_cap), len(f_cap)))
+    lists = {}
+    explained = {}             # file suffix -> arrays
 
     if stream_coarse:                          # the coarse embeddings go to the device once; blocks below are views of them
         dev = torch.device('cuda', torch.cuda.current_device())
@@ -702,24 +711,43 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
         c_cap_dev = torch.from_numpy(np.ascontiguousarray(c_cap)).to(dev)
 
     def block(sl_img, sl_cap, prefix):
+        def factory(j):
+            make = _scan_score_fn if families[j] == 'SCAN' else _sgraf_score_fn
+            f_img, f_cap, f_len = f_embs[j]
+            return lambda: make(fines[j][0], f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
+        factories = [factory(j) for j in range(len(fines))]
+        # the ensemble hands the factories on: one member's device state at a time.  The single form builds its scorer here, where it
+        # always did (before a streamed coarse stage, after a stored one), and keeps it for the explanation.
+        fn = None
         if stream_coarse:
-            fn = fine_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
-            (r, ri, (i_ranks, t_ranks), tl), c_ranks = rerank_streamed(c_img_dev[sl_img].contiguous(), c_cap_dev[sl_cap], coarse_fn, fn, k,
-                                                                       return_coarse_ranks=True)
+            img, cap = c_img_dev[sl_img].contiguous(), c_cap_dev[sl_cap]
+            if ensemble:
+                fine, c_ranks = rerank_ensemble_streamed(img, cap, coarse_fn, factories, k, return_coarse_ranks=True)
+            else:
+                fn = factories[0]()
+                fine, c_ranks = rerank_streamed(img, cap, coarse_fn, fn, k, return_coarse_ranks=True)
             res_c = _recall_dict(c_ranks)
         else:
             sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
             res_c = cal_recall(sims)
-            fn = fine_score_fn(fine, f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
-            r, ri, (i_ranks, t_ranks), tl = rerank(sims.astype(np.float32), fn, k)
+            if ensemble:
+                fine = rerank_ensemble(sims.astype(np.float32), factories, k)
+            else:
+                fn = factories[0]()
+                fine = rerank(sims.astype(np.float32), fn, k)
+        r, ri, (i_ranks, t_ranks), tl = fine
         lists.update({prefix + key: v for key, v in tl.items()})
-        if explain_m is not None:
-            explained.update(_explain_lists(tl, fn, explain_m))
-        if sgraf_m is not None:
-            reasoned.update(_explain_sgraf_lists(tl, fn, sgraf_m))
+        for j, family in enumerate(families):          # (ensemble: one member's state at a time, rebuilt for the explanation)
+            member = '_member%d' % (j + 1) if ensemble else ''
+            if family == 'SCAN' and 'explain' in wanted:
+                explained['explain%d%s' % (wanted['explain'], member)] = _explain_lists(tl, fn or factories[j](), wanted['explain'])
+            if family == 'SGRAF' and 'explain_sgraf' in wanted:
+                explained['explain%d%s_sgraf' % (wanted['explain_sgraf'], member)] = _explain_sgraf_lists(tl, fn or factories[j](),
+                                                                                                         wanted['explain_sgraf'])
         res_r = _recall_dict((i_ranks, tl['i2t_topk'][:, 0], t_ranks, tl['t2i_topk'][:, 0]))
-        print("Reranked (k = %d) image to text: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((k,) + tuple(r)))
-        print("Reranked (k = %d) text to image: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((k,) + tuple(ri)))
+        what = "Ensemble of %d reranked" % len(fines) if ensemble else "Reranked"
+        print("%s (k = %d) image to text: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((what, k) + tuple(r)))
+        print("%s (k = %d) text to image: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((what, k) + tuple(ri)))
         return res_c, res_r
 
     n = len(c_img)
@@ -736,16 +764,18 @@ def evalrank_rerank(model_path_coarse, model_path_fine, k, data_path=None, split
         for key in ('coarse', 'rerank'):
             res_dic[key]['Mean_metrics'] = _mean_metrics(res_dic[key])
     res_dic['data_name'] = c_cfg['data_name'] + ('_5fold' if fold5 else '')
-    res_dic['k'] = int(k)
-    res_dic['modal_path_coarse'], res_dic['modal_path_fine'] = model_path_coarse, model_path_fine
-    save_dir = os.path.dirname(model_path_coarse)
-    with open(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_result.yaml'), 'w') as f:
+    res_dic['k'] = k
+    res_dic['modal_path_coarse'] = model_path_coarse
+    if ensemble:
+        res_dic['modal_paths_fine'] = list(model_paths_fine)
+    else:
+        res_dic['modal_path_fine'] = model_paths_fine[0]
+    stem = os.path.join(os.path.dirname(model_path_coarse), f'{res_dic["data_name"]}_rerank{k}' + ('_ensemble' if ensemble else ''))
+    with open(stem + '_result.yaml', 'w') as f:
         yaml.safe_dump(_plain(res_dic), f)
-    np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}.npz'), **lists)
-    if explain_m is not None:
-        np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_explain{explain_m}.npz'), **explained)
-    if sgraf_m is not None:
-        np.savez(os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{int(k)}_explain{sgraf_m}_sgraf.npz'), **reasoned)
+    np.savez(stem + '.npz', **lists)
+    for suffix, arrays in explained.items():
+        np.savez(stem + '_' + suffix + '.npz', **arrays)
     return res_dic
 
 
@@ -772,13 +802,8 @@ def rerank_ensemble(sims_coarse, score_fns, k, im_div=5):
     / 't2i_topk_member_scores' (float32 [M, n, k]) what each member gave the entries, in the reranked order."""
     score_fns = list(score_fns)
     k = _rerank_args("rerank_ensemble", k, score_fns)
-    S = _device_matrix(sims_coarse)
-    if S.dtype != torch.float32:
-        S = S.to(torch.float32)
-    r_idx, _, part = ops.topk_lists(S, k)
-    c_idx, _ = ops.topk_merge_cols([part], k)
-    i_rank, _, t_rank, _, _ = ops.rank_counts(S, im_div)
-    return _rerank_tail(r_idx, c_idx, i_rank.cpu().numpy(), t_rank.cpu().numpy(), None, score_fns, im_div)
+    r_idx, c_idx, i_rank, t_rank = _materialised_coarse(sims_coarse, k, im_div)
+    return _rerank_tail(r_idx, c_idx, i_rank, t_rank, None, score_fns, im_div)
 
 
 def evalrank_rerank_ensemble(model_path_coarse, model_paths_fine, k, data_path=None, split='dev', fold5=False, explain=None,
@@ -794,109 +819,6 @@ def evalrank_rerank_ensemble(model_path_coarse, model_paths_fine, k, data_path=N
     every SGRAF member (`explain` / `explain_sgraf` on the fused lists, one member at a time), member j (1-based position among
     the fine checkpoints) in `<data_name>_rerank<k>_ensemble_explain<M>_member<j>.npz` / `..._member<j>_sgraf.npz`.
     stream_coarse=True: as in `evalrank_rerank` -- the coarse matrix is never built (`rerank_ensemble_streamed`)."""
-    import os
-    import yaml
-    from ..datamodule import data_loader as data
-    k = int(k)
-    if k < 10:
-        raise ValueError("evalrank_rerank_ensemble: k = %d < 10: R@10 would not be defined by the shortlist" % k)
     model_paths_fine = [model_paths_fine] if isinstance(model_paths_fine, str) else list(model_paths_fine)
-    if not 1 <= len(model_paths_fine) <= 4:
-        raise ValueError("evalrank_rerank_ensemble: 1 to 4 fine checkpoints, got %d" % len(model_paths_fine))
-    wanted = {}
-    for name, m in (('explain', explain), ('explain_sgraf', explain_sgraf)):
-        if m is None:
-            continue
-        if fold5:
-            raise ValueError("evalrank_rerank_ensemble: %s does not combine with fold5" % name)
-        if int(m) < 1 or int(m) > k:
-            raise ValueError("evalrank_rerank_ensemble: %s = %d outside [1, k = %d]" % (name, int(m), k))
-        wanted[name] = int(m)
-    coarse, c_cfg = _load_for_eval(model_path_coarse, data_path)
-    fines = [_load_for_eval(p, data_path) for p in model_paths_fine]
-    for _, f_cfg in fines:
-        if f_cfg['name'] not in ('SCAN', 'SGRAF'):
-            raise NotImplementedError("evalrank_rerank_ensemble: every fine model must be SCAN or SGRAF (candidate-list scoring exists for "
-                                      "these only), got %s" % f_cfg['name'])
-    families = [f_cfg['name'] for _, f_cfg in fines]
-    coarse_fn = _streamed_coarse_scorer(c_cfg['name'], c_cfg, "evalrank_rerank_ensemble") if stream_coarse else None
-    if 'explain' in wanted and 'SCAN' not in families:
-        raise NotImplementedError("evalrank_rerank_ensemble: explain needs a SCAN member (attention maps exist for SCAN only; SGRAF members "
-                                  "explain themselves through explain_sgraf), got %s" % ', '.join(families))
-    if 'explain_sgraf' in wanted and 'SGRAF' not in families:
-        raise NotImplementedError("evalrank_rerank_ensemble: explain_sgraf needs an SGRAF member (SCAN members explain themselves through "
-                                  "explain), got %s" % ', '.join(families))
-    for _, f_cfg in fines:
-        if f_cfg['data_name'] != c_cfg['data_name']:
-            raise ValueError("evalrank_rerank_ensemble: the checkpoints name different datasets (%s, %s): their lists would not index the "
-                             "same items" % (c_cfg['data_name'], f_cfg['data_name']))
-    embs = []
-    for model, cfg in [(coarse, c_cfg)] + fines:
-        loader, _ = data.get_test_loader(split, cfg['data_name'], cfg['batch_size'], cfg['workers'], cfg)
-        embs.append(encode_data(model, loader, islength=cfg['name'] in ['SGRAF', 'SCAN']))
-    (c_img, c_cap, c_len), f_embs = embs[0], embs[1:]
-    for f_img, f_cap, _ in f_embs:
-        if len(c_img) != len(f_img) or len(c_cap) != len(f_cap):
-            raise ValueError("evalrank_rerank_ensemble: the models' loaders hold different item counts (%d / %d images, %d / %d captions)"
-                             % (len(c_img), len(f_img), len(c_cap), len(f_cap)))
-    lists = {}
-    explained = {}             # file suffix -> arrays
-
-    if stream_coarse:
-        dev = torch.device('cuda', torch.cuda.current_device())
-        c_img_dev = torch.from_numpy(np.ascontiguousarray(c_img)).to(dev)
-        c_cap_dev = torch.from_numpy(np.ascontiguousarray(c_cap)).to(dev)
-
-    def block(sl_img, sl_cap, prefix):
-        def factory(j):
-            make = _scan_score_fn if families[j] == 'SCAN' else _sgraf_score_fn
-            f_img, f_cap, f_len = f_embs[j]
-            return lambda: make(fines[j][0], f_img[sl_img], f_cap[sl_cap], f_len[sl_cap])
-        factories = [factory(j) for j in range(len(fines))]
-        if stream_coarse:
-            (r, ri, (i_ranks, t_ranks), tl), c_ranks = rerank_ensemble_streamed(c_img_dev[sl_img].contiguous(), c_cap_dev[sl_cap], coarse_fn,
-                                                                                factories, k, return_coarse_ranks=True)
-            res_c = _recall_dict(c_ranks)
-        else:
-            sims = cal_sims(coarse, c_img[sl_img], c_cap[sl_cap], lengths=c_len[sl_cap], shard_size=c_cfg['batch_size'] * 5)
-            res_c = cal_recall(sims)
-            r, ri, (i_ranks, t_ranks), tl = rerank_ensemble(sims.astype(np.float32), factories, k)
-        lists.update({prefix + key: v for key, v in tl.items()})
-        for j, family in enumerate(families):          # one member's state at a time, rebuilt for the explanation
-            if family == 'SCAN' and 'explain' in wanted:
-                fn = factories[j]()
-                explained['explain%d_member%d' % (wanted['explain'], j + 1)] = _explain_lists(tl, fn, wanted['explain'])
-                del fn
-            if family == 'SGRAF' and 'explain_sgraf' in wanted:
-                fn = factories[j]()
-                explained['explain%d_member%d_sgraf' % (wanted['explain_sgraf'], j + 1)] = _explain_sgraf_lists(tl, fn, wanted['explain_sgraf'])
-                del fn
-        res_r = _recall_dict((i_ranks, tl['i2t_topk'][:, 0], t_ranks, tl['t2i_topk'][:, 0]))
-        print("Ensemble of %d reranked (k = %d) image to text: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((len(fines), k) + tuple(r)))
-        print("Ensemble of %d reranked (k = %d) text to image: r1 %.1f; r5 %.1f; r10 %.1f; medr %.1f; meanr %.1f" % ((len(fines), k) + tuple(ri)))
-        return res_c, res_r
-
-    n = len(c_img)
-    if not fold5:
-        res_c, res_r = block(slice(0, n, 5), slice(None), '')
-        res_dic = {'coarse': res_c, 'rerank': res_r}
-    else:
-        res_dic = {'coarse': {'sum_result': []}, 'rerank': {'sum_result': []}}
-        for i in range(5):
-            res_c, res_r = block(slice(i * 5000, (i + 1) * 5000, 5), slice(i * 5000, (i + 1) * 5000), f'PART_{i + 1}_')
-            for key, part in (('coarse', res_c), ('rerank', res_r)):
-                res_dic[key][f'PART_{i + 1}'] = part
-                res_dic[key]['sum_result'] += part['result']
-        for key in ('coarse', 'rerank'):
-            res_dic[key]['Mean_metrics'] = _mean_metrics(res_dic[key])
-    res_dic['data_name'] = c_cfg['data_name'] + ('_5fold' if fold5 else '')
-    res_dic['k'] = k
-    res_dic['modal_path_coarse'], res_dic['modal_paths_fine'] = model_path_coarse, list(model_paths_fine)
-    save_dir = os.path.dirname(model_path_coarse)
-    stem = os.path.join(save_dir, f'{res_dic["data_name"]}_rerank{k}_ensemble')
-    with open(stem + '_result.yaml', 'w') as f:
-        yaml.safe_dump(_plain(res_dic), f)
-    np.savez(stem + '.npz', **lists)
-    for suffix, arrays in explained.items():
-        np.savez(stem + '_' + suffix + '.npz', **arrays)
-    return res_dic
+    return _evalrank_rerank("evalrank_rerank_ensemble", True, model_path_coarse, model_paths_fine, k, data_path, split, fold5, explain,
+                            explain_sgraf, stream_coarse)

@@ -786,12 +786,7 @@ def _sgraf_workspace(lib, dev, Ni, Nc, n_rows, n_tiles, D, S_dim, mod, flags, im
         wsb = lib.itr_sgraf_workspace_bytes(Ni, Nc, n_rows, n_tiles, D, S_dim, mod, int(image_block), flags)
         SGRAF_LAST_BLOCK.update(image_block=int(image_block), workspace_bytes=int(wsb), budget_bytes=None, pinned=True)
         return torch.empty(wsb, device=dev, dtype=torch.uint8), int(image_block)
-    if max_workspace_bytes is None:
-        free, _total = torch.cuda.mem_get_info(dev)
-        cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        budget = int(0.9 * (free + cached))
-    else:
-        budget = int(max_workspace_bytes)
+    budget = _workspace_budget(dev, max_workspace_bytes)
     while True:
         wsb = C.c_size_t(0)
         ib = lib.itr_sgraf_pick_image_block(Ni, Nc, n_rows, n_tiles, D, S_dim, mod, flags, max(0, budget), C.byref(wsb))
@@ -1168,15 +1163,172 @@ def topk_fold_cols(S_block, k, row0=0, state=None):
 
 
 # ------------------------------------------------------------------------------------------ candidate lists (coarse-to-fine retrieval)
-def _pairs_state(plan, dev):
-    """Device copies of ALL captions' offsets and lengths for the pair kernel (a ScanPlan keeps only those of the captions its
-    column tiles hold); captions of more than SCAN_NT words get length 0 = "not scored by the kernel".  Cached on the plan."""
-    st = getattr(plan, "_pairs_state", None)
-    if st is None or st[0] != dev:
-        klen = np.where(plan.len_host > SCAN_NT, 0, plan.len_host).astype(np.int32)
-        st = (dev, h2d(np.asarray(plan.off_host, dtype=np.int64), dev), h2d(klen, dev))
-        plan._pairs_state = st
-    return st[1], st[2]
+# The list and pair plumbing every candidate op below shares (SCAN / SGRAF scores, SCAN / SGRAF explanations).  `who` is the public
+# function the messages name.
+def _caption_tables(plan, dev, max_words):
+    """Device copies of ALL captions' offsets (int64) and lengths (int32) (a ScanPlan keeps only those of the captions its column
+    tiles hold) -> (off, lens).  Lengths above `max_words` become 0 = "not taken by the kernel"; max_words=None: the true lengths.
+    Cached on the plan per device (offsets) and per (device, max_words) (lengths)."""
+    cache = getattr(plan, "_caption_tables", None)
+    if cache is None:
+        cache = plan._caption_tables = {}
+    if (dev, 'off') not in cache:
+        cache[dev, 'off'] = h2d(np.asarray(plan.off_host, dtype=np.int64), dev)
+    if (dev, max_words) not in cache:
+        lens = plan.len_host if max_words is None else np.where(plan.len_host > max_words, 0, plan.len_host)
+        cache[dev, max_words] = h2d(np.asarray(lens, dtype=np.int32), dev)
+    return cache[dev, 'off'], cache[dev, max_words]
+
+
+def _check_by(who, by):
+    if by not in ('caption', 'image'):
+        raise ValueError("%s: by must be 'caption' or 'image', got %r" % (who, by))
+
+
+def _check_lists(who, cand, by, images, plan):
+    """cand is an int32 device tensor [n_q, K] with one list per caption (by='caption') or per image -> (n_q, n_t, K): the number
+    of queries (lists), of targets (what a list indexes) and the list length.  Copies nothing: a view is made contiguous by the
+    caller, after the shape checks."""
+    if not torch.is_tensor(cand) or not cand.is_cuda or cand.dtype != torch.int32:
+        _dev(cand, torch.int32, name="cand")                      # (raises)
+    if cand.dim() != 2:
+        raise ValueError("%s: cand must be 2-D, got shape %s" % (who, tuple(cand.shape)))
+    Ni, Nc = images.shape[0], plan.Nc
+    n_q, n_t = (Nc, Ni) if by == 'caption' else (Ni, Nc)
+    if cand.shape[0] != n_q:
+        raise ValueError("%s: by=%r needs %d lists, got %d" % (who, by, n_q, cand.shape[0]))
+    return n_q, n_t, cand.shape[1]
+
+
+def _check_in_range(who, idx, bound):
+    """One device reduction, so that nothing out of range reaches a kernel.  bound = n: the entries of the lists `idx` lie in
+    [0, n); bound = (Ni, Nc): the columns of the [P, 2] pairs `idx` lie in [0, Ni) and [0, Nc)."""
+    if isinstance(bound, tuple):
+        Ni, Nc = bound
+        lo, hi = torch.aminmax(idx, dim=0)
+        (ilo, clo), (ihi, chi) = lo.tolist(), hi.tolist()
+        if ilo < 0 or ihi >= Ni or clo < 0 or chi >= Nc:
+            raise ValueError("%s: pair index out of range: images [%d, %d] of %d, captions [%d, %d] of %d" % (who, ilo, ihi, Ni, clo, chi, Nc))
+    else:
+        lo, hi = torch.aminmax(idx)
+        lo, hi = int(lo), int(hi)
+        if lo < 0 or hi >= bound:
+            raise ValueError("%s: candidate index out of range [0, %d): min %d, max %d" % (who, bound, lo, hi))
+
+
+def _lists_to_pairs(who, cand, by, n_q, m):
+    """The first `m` columns of every list (all of them when m is None) as int32 [n_q m, 2] (image, caption) pairs: pair q * m + k
+    is list q's entry k."""
+    m = cand.shape[1] if m is None else int(m)
+    if m < 0 or m > cand.shape[1]:
+        raise ValueError("%s: m = %d outside [0, %d]" % (who, m, cand.shape[1]))
+    flat = cand[:, :m].reshape(-1)
+    qid = torch.arange(n_q, device=cand.device, dtype=torch.int32).repeat_interleave(m)
+    return torch.stack((flat, qid) if by == 'caption' else (qid, flat), 1)
+
+
+def _flat_pairs(cand, by, n_q, K):
+    """Lists -> (caps, imgs, slot), int64 [n_q K] on the lists' device: the caption and the image of every entry, and its place in
+    the flattened result."""
+    flat = cand.reshape(-1).to(torch.int64)
+    qid = torch.arange(n_q, device=cand.device, dtype=torch.int64).repeat_interleave(K)
+    caps, imgs = (qid, flat) if by == 'caption' else (flat, qid)
+    return caps, imgs, torch.arange(n_q * K, device=cand.device, dtype=torch.int64)
+
+
+def _group_pairs(key, n_keys, cols, grouped):
+    """Pairs -> CSR form by `key` (int64 [P], values in [0, n_keys)): -> (ptr int32 [n_keys + 1], key, *cols) with the pairs of key
+    j at ptr[j] .. ptr[j + 1], in their incoming order (stable sort), and `cols` (tensors [P]) carried along.  grouped=True: the
+    caller knows the keys already ascend (lists flattened by their own query), no sort is launched.  No pairs: only the zero
+    pointer is made.  Works on host tensors too."""
+    if key.numel() and not grouped:
+        key, order = torch.sort(key, stable=True)
+        cols = [c[order] for c in cols]
+    ptr = torch.zeros(n_keys + 1, device=key.device, dtype=torch.int32)
+    if key.numel():
+        ptr[1:] = torch.cumsum(torch.bincount(key, minlength=n_keys), 0).to(torch.int32)
+    return (ptr, key) + tuple(cols)
+
+
+def _long_caption_pairs(images, words, plan, lm, caps, imgs, slot, out, make_col):
+    """The listed pairs of captions too long for a pair kernel (mask `lm` over the pairs) are scored one caption at a time on that
+    caption's listed images and scattered into `out`'s slots: make_col() -> col(images [n, R, D], words [l, D], l) -> the n scores.
+    It is called only when there are such pairs.  -> (caps, imgs, slot) of the other pairs."""
+    lcaps, limgs, lslot = caps[lm], imgs[lm], slot[lm]
+    if lcaps.numel():
+        col = make_col()
+        flat = out.view(-1)
+        with torch.no_grad():
+            for c in torch.unique(lcaps).tolist():
+                m = lcaps == c
+                sel, inv = torch.unique(limgs[m], return_inverse=True)
+                o, l = int(plan.off_host[c]), int(plan.len_host[c])
+                flat[lslot[m]] = col(images[sel].contiguous(), words[o:o + l].contiguous(), l).reshape(-1)[inv]
+    return caps[~lm], imgs[~lm], slot[~lm]
+
+
+def _sgraf_item_plan(lib, img_ptr, pair_cap, off, klen, P, Ni, Nc, n_rows, dev):
+    """itr_sgraf_pairs_plan on image-major pairs -> (pair_len, pair_col, pair_capok, item_begin, item_img) int32 on the device,
+    n_items, and item_begin[:n_items + 1] on the host (int64): the chunk bounds need it, the plan's one read-back."""
+    pair_len, pair_col, pair_capok = (torch.empty(P, device=dev, dtype=torch.int32) for _ in range(3))
+    item_begin = torch.empty(P + 1, device=dev, dtype=torch.int32)
+    item_img = torch.empty(P, device=dev, dtype=torch.int32)
+    n_items_dev = torch.zeros(1, device=dev, dtype=torch.int32)
+    pwb = lib.itr_sgraf_pairs_plan_workspace_bytes(Ni)
+    pws = torch.empty(max(pwb, 1), device=dev, dtype=torch.uint8)
+    _lib.check(lib.itr_sgraf_pairs_plan(_p(img_ptr), _p(pair_cap), _p(off), _p(klen), P, Ni, Nc, n_rows, _p(pair_len), _p(pair_col),
+                                        _p(pair_capok), _p(item_begin), _p(item_img), _p(n_items_dev), _p(pws), pwb, _stream()))
+    n_items = int(n_items_dev)
+    return (pair_len, pair_col, pair_capok, item_begin, item_img), n_items, item_begin[:n_items + 1].cpu().numpy().astype(np.int64)
+
+
+def _workspace_budget(dev, max_workspace_bytes):
+    """The bytes a chunk's workspace may take: the caller's limit, or 90 % of the device's free + cached memory"""
+    if max_workspace_bytes is not None:
+        return int(max_workspace_bytes)
+    free, _total = torch.cuda.mem_get_info(dev)
+    cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    return int(0.9 * (free + cached))
+
+
+def _chunks_within(who, need, n_items, budget):
+    """[0, n_items) cut into the fewest chunks (it0, it1) of whole items with need(it0, it1) <= budget bytes, every chunk as long as
+    fits; `need` is monotone in it1.  Host arithmetic only.  An item that does not fit alone: torch.cuda.OutOfMemoryError."""
+    chunks, it0 = [], 0
+    while it0 < n_items:
+        if need(it0, it0 + 1) > budget:
+            raise torch.cuda.OutOfMemoryError("%s: one item needs %d bytes of workspace, %d allowed" % (who, need(it0, it0 + 1), budget))
+        lo, hi = it0 + 1, n_items                               # the largest it1 whose chunk fits
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if need(it0, mid) <= budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        chunks.append((it0, lo))
+        it0 = lo
+    return chunks
+
+
+class _PairBlocks:
+    """What ScanPairAttention and SgrafPairAttention share: the pair count and the bounds-checked host view of a block pointer"""
+
+    def __len__(self):
+        return self.score.shape[0]
+
+    def _pair(self, p):
+        p = int(p)
+        if not 0 <= p < len(self):
+            raise IndexError("pair %d of %d" % (p, len(self)))
+        return p
+
+    def _span(self, name, p):
+        """(begin, end) of pair p in the flat tensor that the pointer `name` indexes; the pointer is read back once"""
+        p = self._pair(p)
+        if name not in self._host:
+            self._host[name] = getattr(self, name).cpu().numpy()
+        ptr = self._host[name]
+        return int(ptr[p]), int(ptr[p + 1])
 
 
 class ScanPairsWorkspace:
@@ -1212,7 +1364,7 @@ def scan_pairs_prepare(images, words, plan, cross_attn='t2i'):
     if R != SCAN_R:
         raise NotImplementedError("scan_pairs_prepare: %d regions per image (the pair kernel is built for %d)" % (R, SCAN_R))
     mode = 0 if cross_attn == 't2i' else 1
-    off, klen = _pairs_state(plan, images.device)
+    off, klen = _caption_tables(plan, images.device, SCAN_NT)
     wsb = lib.itr_scan_pairs_workspace_bytes(Ni, R, words.shape[0], plan.Nc, mode)
     ws = torch.empty(max(wsb, 1), device=images.device, dtype=torch.uint8)
     _lib.check(lib.itr_scan_pairs_prepare(_p(images), _p(words), _p(off), _p(klen), Ni, plan.Nc, words.shape[0], R, D, mode, _p(ws), wsb,
@@ -1231,61 +1383,43 @@ def scan_candidate_scores(images, words, plan, cand, by, cross_attn='t2i', raw_f
     path of the training kernels on their listed images (correct, not fast).  `workspace`: scan_pairs_prepare's, to reuse it."""
     lib = _lib.load()
     if cross_attn not in ('t2i', 'i2t'):
-        raise ValueError("unknown first norm type:", raw_feature_norm)
+        raise ValueError("unknown first norm type:", raw_feature_norm)      # (the reference's message for a bad cross_attn: kept)
     if raw_feature_norm not in _NORMS:
         raise ValueError("unknown first norm type:", raw_feature_norm)
     if agg_func not in _AGGS:
         raise ValueError("unknown aggfunc: {}".format(agg_func))
-    if by not in ('caption', 'image'):
-        raise ValueError("scan_candidate_scores: by must be 'caption' or 'image', got %r" % (by,))
+    _check_by("scan_candidate_scores", by)
     images = _dev(images, name="images")
     words = _dev(words, name="words")
-    cand = _dev(cand, torch.int32, name="cand")
-    if cand.dim() != 2:
-        raise ValueError("scan_candidate_scores: cand must be 2-D, got shape %s" % (tuple(cand.shape),))
+    n_q, n_t, K = _check_lists("scan_candidate_scores", cand, by, images, plan)
+    cand = cand.contiguous()
     Ni, R, D = images.shape
     Nc = plan.Nc
     dev = images.device
-    n_q, n_t = (Nc, Ni) if by == 'caption' else (Ni, Nc)          # queries (lists), targets (what a list indexes)
-    if cand.shape[0] != n_q:
-        raise ValueError("scan_candidate_scores: by=%r needs %d lists, got %d" % (by, n_q, cand.shape[0]))
-    K = cand.shape[1]
     out = torch.empty(n_q, K, device=dev, dtype=torch.float32)
-    if n_q == 0 or K == 0:
+    if n_q == 0 or K == 0:                                        # (before `workspace` is looked at, unlike the ops below: kept)
         return out
     if R != SCAN_R:
         raise NotImplementedError("scan_candidate_scores: %d regions per image (the pair kernel is built for %d)" % (R, SCAN_R))
     if len(plan.len_host) and int(plan.len_host.max()) > SCAN_PAIR_MAXW:
         raise NotImplementedError("scan_candidate_scores: captions of %d words (supported: <= %d)" % (int(plan.len_host.max()), SCAN_PAIR_MAXW))
-    lo, hi = torch.aminmax(cand)                                  # one device reduction: nothing out of range reaches the kernel
-    lo, hi = int(lo), int(hi)
-    if lo < 0 or hi >= n_t:
-        raise ValueError("scan_candidate_scores: candidate index out of range [0, %d): min %d, max %d" % (n_t, lo, hi))
+    _check_in_range("scan_candidate_scores", cand, n_t)
     if n_q * K >= 2 ** 31:
         raise NotImplementedError("scan_candidate_scores: %d pairs; split the lists" % (n_q * K))
     # ---- caption-major (CSR) form, on the device: no dense intermediate
-    flat = cand.reshape(-1).to(torch.int64)
-    qid = torch.arange(n_q, device=dev, dtype=torch.int64).repeat_interleave(K)
-    caps, imgs = (qid, flat) if by == 'caption' else (flat, qid)
-    slot = torch.arange(n_q * K, device=dev, dtype=torch.int64)
+    caps, imgs, slot = _flat_pairs(cand, by, n_q, K)
     if plan.long_idx is not None:
         is_long = torch.zeros(Nc, device=dev, dtype=torch.bool)
         is_long[h2d(plan.long_idx, dev)] = True
-        lm = is_long[caps]
-        _scan_long_caption_pairs(images, words, plan, caps[lm], imgs[lm], slot[lm], out, cross_attn, raw_feature_norm, agg_func,
-                                 lambda_lse, lambda_softmax)
-        caps, imgs, slot = caps[~lm], imgs[~lm], slot[~lm]
-    if by == 'image' and caps.numel():
-        caps, order = torch.sort(caps, stable=True)
-        imgs, slot = imgs[order], slot[order]
+        caps, imgs, slot = _long_caption_pairs(images, words, plan, is_long[caps], caps, imgs, slot, out,
+                                               lambda: _scan_long_caption_col(cross_attn, raw_feature_norm, agg_func, lambda_lse, lambda_softmax))
     P = caps.numel()
     if P == 0:
         return out
-    cap_ptr = torch.zeros(Nc + 1, device=dev, dtype=torch.int32)
-    cap_ptr[1:] = torch.cumsum(torch.bincount(caps, minlength=Nc), 0).to(torch.int32)
+    cap_ptr, caps, imgs, slot = _group_pairs(caps, Nc, (imgs, slot), grouped=by == 'caption')
     pair_img, pair_out = imgs.to(torch.int32), slot.to(torch.int32)
     mode = 0 if cross_attn == 't2i' else 1
-    off, klen = _pairs_state(plan, dev)
+    off, klen = _caption_tables(plan, dev, SCAN_NT)
     if workspace is not None:
         if not isinstance(workspace, ScanPairsWorkspace):
             raise TypeError("scan_candidate_scores: workspace must come from scan_pairs_prepare")
@@ -1299,7 +1433,7 @@ def scan_candidate_scores(images, words, plan, cand, by, cross_attn='t2i', raw_f
 
 
 # ------------------------------------------------------------------------------------------ SCAN attention maps of listed pairs
-class ScanPairAttention:
+class ScanPairAttention(_PairBlocks):
     """What `scan_pair_attention` returns for P pairs: `attn` float32 (flat; pair p holds its [W_p, 36] row-major block at
     attn_ptr[p]), `attn_ptr` int64 [P + 1], `row_sim` float32 (t2i: W_p cosines per pair at row_ptr[p]; i2t: 36 per pair at
     36 p), `row_ptr` int64 [P + 1], `score` float32 [P], `cap_len` int32 [P] (W_p), all on the device, and `pairs` int32 [P, 2]."""
@@ -1307,42 +1441,20 @@ class ScanPairAttention:
     def __init__(self, pairs, attn, attn_ptr, row_sim, row_ptr, score, cap_len, cross_attn):
         self.pairs, self.attn, self.attn_ptr, self.row_sim, self.row_ptr = pairs, attn, attn_ptr, row_sim, row_ptr
         self.score, self.cap_len, self.cross_attn = score, cap_len, cross_attn
-        self._ptr_host = None
-
-    def __len__(self):
-        return self.score.shape[0]
-
-    def _ptr(self):
-        if self._ptr_host is None:
-            self._ptr_host = self.attn_ptr.cpu().numpy()
-        return self._ptr_host
+        self._host = {}
 
     def matrix(self, p):
         """the [W, R] attention matrix of pair p (a view): word-major, t2i rows / i2t columns sum to 1"""
-        p = int(p)
-        if not 0 <= p < len(self):
-            raise IndexError("pair %d of %d" % (p, len(self)))
-        ptr = self._ptr()
-        return self.attn[int(ptr[p]):int(ptr[p + 1])].view(-1, SCAN_R)
+        b, e = self._span('attn_ptr', p)
+        return self.attn[b:e].view(-1, SCAN_R)
 
     def sims(self, p):
         """the cosine similarities pair p's score is aggregated from: one per word (t2i) or per region (i2t)"""
-        p = int(p)
-        if not 0 <= p < len(self):
-            raise IndexError("pair %d of %d" % (p, len(self)))
         if self.cross_attn == 'i2t':
+            p = self._pair(p)
             return self.row_sim[p * SCAN_R:(p + 1) * SCAN_R]
-        ptr = self._ptr()
-        return self.row_sim[int(ptr[p]) // SCAN_R:int(ptr[p + 1]) // SCAN_R]
-
-
-def _attn_lens(plan, dev):
-    """Device copy of ALL captions' true lengths (`_pairs_state` zeroes those the score kernel does not take).  Cached on the plan."""
-    st = getattr(plan, "_attn_lens", None)
-    if st is None or st[0] != dev:
-        st = (dev, h2d(np.asarray(plan.len_host, dtype=np.int32), dev))
-        plan._attn_lens = st
-    return st[1]
+        b, e = self._span('attn_ptr', p)
+        return self.row_sim[b // SCAN_R:e // SCAN_R]
 
 
 def scan_pair_attention(images, words, plan, pairs, cross_attn='t2i', raw_feature_norm='clipped_l2norm', agg_func='LogSumExp',
@@ -1354,7 +1466,7 @@ def scan_pair_attention(images, words, plan, pairs, cross_attn='t2i', raw_featur
     `workspace` (scan_pairs_prepare's) as scan_candidate_scores."""
     lib = _lib.load()
     if cross_attn not in ('t2i', 'i2t'):
-        raise ValueError("unknown first norm type:", raw_feature_norm)
+        raise ValueError("unknown first norm type:", raw_feature_norm)      # (the reference's message for a bad cross_attn: kept)
     if raw_feature_norm not in _NORMS:
         raise ValueError("unknown first norm type:", raw_feature_norm)
     if agg_func not in _AGGS:
@@ -1383,13 +1495,8 @@ def scan_pair_attention(images, words, plan, pairs, cross_attn='t2i', raw_featur
         raise NotImplementedError("scan_pair_attention: captions of %d words (supported: <= %d)" % (int(plan.len_host.max()), SCAN_PAIR_MAXW))
     if P * SCAN_PAIR_MAXW * SCAN_R >= 2 ** 31:
         raise NotImplementedError("scan_pair_attention: %d pairs; split the list" % P)
-    lo, hi = torch.aminmax(pairs, dim=0)                          # one device reduction: nothing out of range reaches the kernel
-    (ilo, clo), (ihi, chi) = lo.tolist(), hi.tolist()
-    if ilo < 0 or ihi >= Ni or clo < 0 or chi >= Nc:
-        raise ValueError("scan_pair_attention: pair index out of range: images [%d, %d] of %d, captions [%d, %d] of %d"
-                         % (ilo, ihi, Ni, clo, chi, Nc))
-    lens = _attn_lens(plan, dev)
-    off, _ = _pairs_state(plan, dev)
+    _check_in_range("scan_pair_attention", pairs, (Ni, Nc))
+    off, lens = _caption_tables(plan, dev, None)
     pair_img, pair_cap = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
     cap_len = lens[pair_cap.long()]
     row_ptr = torch.zeros(P + 1, device=dev, dtype=torch.int64)
@@ -1410,35 +1517,13 @@ def scan_pair_attention(images, words, plan, pairs, cross_attn='t2i', raw_featur
 def scan_candidate_attention(images, words, plan, cand, by, m=None, **kw):
     """`scan_pair_attention` for candidate lists, `cand` and `by` as in scan_candidate_scores: explains the first `m` columns of
     every list (all of them when m is None) -> ScanPairAttention whose pair q * m + k is list q's entry k."""
-    if by not in ('caption', 'image'):
-        raise ValueError("scan_candidate_attention: by must be 'caption' or 'image', got %r" % (by,))
-    cand = _dev(cand, torch.int32, name="cand")
-    if cand.dim() != 2:
-        raise ValueError("scan_candidate_attention: cand must be 2-D, got shape %s" % (tuple(cand.shape),))
-    n_q = plan.Nc if by == 'caption' else images.shape[0]
-    if cand.shape[0] != n_q:
-        raise ValueError("scan_candidate_attention: by=%r needs %d lists, got %d" % (by, n_q, cand.shape[0]))
-    m = cand.shape[1] if m is None else int(m)
-    if m < 0 or m > cand.shape[1]:
-        raise ValueError("scan_candidate_attention: m = %d outside [0, %d]" % (m, cand.shape[1]))
-    flat = cand[:, :m].reshape(-1)
-    qid = torch.arange(n_q, device=cand.device, dtype=torch.int32).repeat_interleave(m)
-    pairs = torch.stack((flat, qid) if by == 'caption' else (qid, flat), 1)
+    _check_by("scan_candidate_attention", by)
+    n_q, _, _ = _check_lists("scan_candidate_attention", cand, by, images, plan)
+    pairs = _lists_to_pairs("scan_candidate_attention", cand.contiguous(), by, n_q, m)
     return scan_pair_attention(images, words, plan, pairs, **kw)
 
 
 # ------------------------------------------------------------------------------------------ SGRAF on candidate lists
-def _sgraf_pairs_lens(plan, dev):
-    """Device copies of ALL captions' offsets and lengths for the SGRAF pair kernels; captions of more than SGRAF_MAX_WORDS words get
-    length 0 = "not scored by the kernels".  Cached on the plan."""
-    st = getattr(plan, "_sgraf_pairs_lens", None)
-    if st is None or st[0] != dev:
-        klen = np.where(plan.len_host > SGRAF_MAX_WORDS, 0, plan.len_host).astype(np.int32)
-        st = (dev, h2d(np.asarray(plan.off_host, dtype=np.int64), dev), h2d(klen, dev))
-        plan._sgraf_pairs_lens = st
-    return st[1], st[2]
-
-
 class SgrafPairsState:
     """What `sgraf_pairs_prepare` computed and for what: the buffer (VisualSA / TextSA global vectors, the images' Gram matrices, SGR's
     folded and packed weights) and the identity of the operands, the weights and the module.  `sgraf_candidate_scores` refuses a state
@@ -1479,7 +1564,7 @@ def sgraf_pairs_prepare(images, words, plan, weights, module_name='SAF', sgr_ste
         raise NotImplementedError("sgraf_candidate_scores: captions of at most %d words are supported" % SGRAF_COMPOSED_MAX_WORDS)
     st, keep, S_dim = _sgraf_weight_struct(weights, module_name, sgr_step)
     mod = 0 if module_name == 'SAF' else 1
-    off, klen = _sgraf_pairs_lens(plan, images.device)
+    off, klen = _caption_tables(plan, images.device, SGRAF_MAX_WORDS)
     nb = lib.itr_sgraf_pairs_state_bytes(Ni, plan.Nc, words.shape[0], D, S_dim, mod, int(sgr_step))
     buf = torch.empty(max(nb, 1), device=images.device, dtype=torch.uint8)
     sb = lib.itr_sgraf_pairs_prepare_scratch_bytes(Ni, plan.Nc, words.shape[0], D, S_dim, mod)
@@ -1508,21 +1593,13 @@ def sgraf_candidate_scores(images, words, plan, weights, cand, by, module_name='
     lib = _lib.load()
     if module_name not in ('SAF', 'SGR'):
         raise ValueError('Invalid input of config.module_name in configs.py')
-    if by not in ('caption', 'image'):
-        raise ValueError("sgraf_candidate_scores: by must be 'caption' or 'image', got %r" % (by,))
+    _check_by("sgraf_candidate_scores", by)
     images = _dev(images, name="images")
     words = _dev(words, name="words")
-    if not torch.is_tensor(cand) or not cand.is_cuda or cand.dtype != torch.int32:
-        _dev(cand, torch.int32, name="cand")                      # (raises; a view is made contiguous only after the shape checks)
-    if cand.dim() != 2:
-        raise ValueError("sgraf_candidate_scores: cand must be 2-D, got shape %s" % (tuple(cand.shape),))
+    n_q, n_t, K = _check_lists("sgraf_candidate_scores", cand, by, images, plan)
     Ni, R, D = images.shape
     Nc = plan.Nc
     dev = images.device
-    n_q, n_t = (Nc, Ni) if by == 'caption' else (Ni, Nc)
-    if cand.shape[0] != n_q:
-        raise ValueError("sgraf_candidate_scores: by=%r needs %d lists, got %d" % (by, n_q, cand.shape[0]))
-    K = cand.shape[1]
     if n_q * K >= 2 ** 31 // 64:
         raise NotImplementedError("sgraf_candidate_scores: %d pairs (at most %d per call); split the lists" % (n_q * K, 2 ** 31 // 64 - 1))
     cand = cand.contiguous()
@@ -1537,70 +1614,35 @@ def sgraf_candidate_scores(images, words, plan, weights, cand, by, module_name='
         raise NotImplementedError("sgraf_candidate_scores: %d regions per image (VisualSA is built for %d)" % (R, SCAN_R))
     if len(plan.len_host) and int(plan.len_host.max()) > SGRAF_COMPOSED_MAX_WORDS:
         raise NotImplementedError("sgraf_candidate_scores: captions of at most %d words are supported" % SGRAF_COMPOSED_MAX_WORDS)
-    lo, hi = torch.aminmax(cand)
-    lo, hi = int(lo), int(hi)
-    if lo < 0 or hi >= n_t:
-        raise ValueError("sgraf_candidate_scores: candidate index out of range [0, %d): min %d, max %d" % (n_t, lo, hi))
+    _check_in_range("sgraf_candidate_scores", cand, n_t)
     if state is None:
         state = sgraf_pairs_prepare(images, words, plan, weights, module_name, sgr_step)
     S_dim, st = state.S_dim, state.struct
     mod = 0 if module_name == 'SAF' else 1
     # ---- image-major (CSR) form, on the device: no dense intermediate
-    flat = cand.reshape(-1).to(torch.int64)
-    qid = torch.arange(n_q, device=dev, dtype=torch.int64).repeat_interleave(K)
-    caps, imgs = (qid, flat) if by == 'caption' else (flat, qid)
-    slot = torch.arange(n_q * K, device=dev, dtype=torch.int64)
+    caps, imgs, slot = _flat_pairs(cand, by, n_q, K)
     if len(plan.len_host) and int(plan.len_host.max()) > SGRAF_MAX_WORDS:
         is_long = h2d(plan.len_host > SGRAF_MAX_WORDS, dev)
-        lm = is_long[caps]
-        _sgraf_long_caption_pairs(images, words, plan, weights, module_name, sgr_step, S_dim, caps[lm], imgs[lm], slot[lm], out)
-        caps, imgs, slot = caps[~lm], imgs[~lm], slot[~lm]
-    if by == 'caption' and caps.numel():
-        imgs, order = torch.sort(imgs, stable=True)
-        caps, slot = caps[order], slot[order]
+        caps, imgs, slot = _long_caption_pairs(images, words, plan, is_long[caps], caps, imgs, slot, out,
+                                               lambda: _sgraf_long_caption_col(images, weights, module_name, sgr_step, S_dim))
     P = caps.numel()
     if P == 0:
         return out
-    img_ptr = torch.zeros(Ni + 1, device=dev, dtype=torch.int32)
-    img_ptr[1:] = torch.cumsum(torch.bincount(imgs, minlength=Ni), 0).to(torch.int32)
+    img_ptr, imgs, caps, slot = _group_pairs(imgs, Ni, (caps, slot), grouped=by == 'image')
     pair_img, pair_cap, pair_out = imgs.to(torch.int32), caps.to(torch.int32), slot.to(torch.int32)
-    off, klen = _sgraf_pairs_lens(plan, dev)
-    pair_len, pair_col, pair_capok = (torch.empty(P, device=dev, dtype=torch.int32) for _ in range(3))
-    item_begin = torch.empty(P + 1, device=dev, dtype=torch.int32)
-    item_img = torch.empty(P, device=dev, dtype=torch.int32)
-    n_items_dev = torch.zeros(1, device=dev, dtype=torch.int32)
-    pwb = lib.itr_sgraf_pairs_plan_workspace_bytes(Ni)
-    pws = torch.empty(max(pwb, 1), device=dev, dtype=torch.uint8)
-    _lib.check(lib.itr_sgraf_pairs_plan(_p(img_ptr), _p(pair_cap), _p(off), _p(klen), P, Ni, Nc, words.shape[0], _p(pair_len), _p(pair_col),
-                                        _p(pair_capok), _p(item_begin), _p(item_img), _p(n_items_dev), _p(pws), pwb, _stream()))
-    n_items = int(n_items_dev)                                  # (the one host read-back of the plan: chunk bounds need it)
-    ib = item_begin[:n_items + 1].cpu().numpy().astype(np.int64)
+    off, klen = _caption_tables(plan, dev, SGRAF_MAX_WORDS)
+    (pair_len, pair_col, pair_capok, item_begin, item_img), n_items, ib = _sgraf_item_plan(lib, img_ptr, pair_cap, off, klen, P, Ni, Nc,
+                                                                                          words.shape[0], dev)
     # ---- chunks of whole items sized to the budget
-    if max_workspace_bytes is None:
-        free, _total = torch.cuda.mem_get_info(dev)
-        cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        budget = int(0.9 * (free + cached))
-    else:
-        budget = int(max_workspace_bytes)
+    budget = _workspace_budget(dev, max_workspace_bytes)
 
     def need(it0, it1):
         return lib.itr_sgraf_pair_scores_workspace_bytes(int(ib[it1] - ib[it0]), it1 - it0, D, S_dim, mod, int(sgr_step))
 
-    chunks, it0 = [], 0
-    while it0 < n_items:
-        if need(it0, it0 + 1) > budget:
-            raise torch.cuda.OutOfMemoryError("sgraf_candidate_scores: one item needs %d bytes of workspace, %d allowed" % (need(it0, it0 + 1), budget))
-        lo_, hi_ = it0 + 1, n_items                             # the largest it1 whose chunk fits (need is monotone)
-        while lo_ < hi_:
-            mid = (lo_ + hi_ + 1) // 2
-            if need(it0, mid) <= budget:
-                lo_ = mid
-            else:
-                hi_ = mid - 1
-        chunks.append((it0, lo_))
-        it0 = lo_
+    chunks = _chunks_within("sgraf_candidate_scores", need, n_items, budget)
     wsb = max(need(a, b) for a, b in chunks)
     ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+    # (written only here: an early return above leaves the previous call's figures, unlike SGRAF_ATTN_LAST: kept)
     SGRAF_PAIRS_LAST.update(pairs=P, items=n_items, chunks=len(chunks), workspace_bytes=int(wsb), budget_bytes=budget)
     for a, b in chunks:
         _lib.check(lib.itr_sgraf_pair_scores(_p(images), _p(words), _p(off), _p(pair_img), _p(pair_capok), _p(pair_len), _p(pair_col), _p(pair_out),
@@ -1614,7 +1656,7 @@ def sgraf_candidate_scores(images, words, plan, weights, cand, by, module_name='
 SGRAF_ATTN_MAX_SIM_DIM = 256   # csrc/sgraf_attn.hip keeps an item's node rows on chip
 
 
-class SgrafPairAttention:
+class SgrafPairAttention(_PairBlocks):
     """What `sgraf_pair_attention` returns for P pairs, all on the device, in the caller's order.  Pair p has W_p words and
     n_p = W_p + 1 alignment nodes; NODE 0 IS THE GLOBAL NODE, node 1 + w is word w.
       attn / attn_ptr     float32 flat / int64 [P + 1]: the [W_p, 36] row-major SCAN_attention weights (rows sum to 1)
@@ -1628,18 +1670,6 @@ class SgrafPairAttention:
         self.edge, self.edge_ptr, self.score, self.cap_len, self.explained = edge, edge_ptr, score, cap_len, explained
         self.module_name, self.sgr_step = module_name, int(sgr_step)
         self._host = {}
-
-    def __len__(self):
-        return self.score.shape[0]
-
-    def _span(self, name, p):
-        p = int(p)
-        if not 0 <= p < len(self):
-            raise IndexError("pair %d of %d" % (p, len(self)))
-        if name not in self._host:
-            self._host[name] = getattr(self, name).cpu().numpy()
-        ptr = self._host[name]
-        return int(ptr[p]), int(ptr[p + 1])
 
     def matrix(self, p):
         """the [W, 36] word x region attention of pair p (a view); [0, 36] for a pair that is not explained"""
@@ -1707,18 +1737,14 @@ def sgraf_pair_attention(images, words, plan, weights, pairs, module_name='SAF',
         raise NotImplementedError("sgraf_pair_attention: captions of at most %d words are supported" % SGRAF_COMPOSED_MAX_WORDS)
     if P >= 2 ** 31 // 64:
         raise NotImplementedError("sgraf_pair_attention: %d pairs (at most %d per call); split the list" % (P, 2 ** 31 // 64 - 1))
-    lo, hi = torch.aminmax(pairs, dim=0)                          # one device reduction: nothing out of range reaches the kernels
-    (ilo, clo), (ihi, chi) = lo.tolist(), hi.tolist()
-    if ilo < 0 or ihi >= Ni or clo < 0 or chi >= Nc:
-        raise ValueError("sgraf_pair_attention: pair index out of range: images [%d, %d] of %d, captions [%d, %d] of %d"
-                         % (ilo, ihi, Ni, clo, chi, Nc))
+    _check_in_range("sgraf_pair_attention", pairs, (Ni, Nc))
     if state is None:
         state = sgraf_pairs_prepare(images, words, plan, weights, module_name, sgr_step)
     st = state.struct
     mod = 1 if sgr else 0
     # ---- the output layout, on the device
     imgs, caps = pairs[:, 0].to(torch.int64), pairs[:, 1].to(torch.int64)
-    cap_len = _attn_lens(plan, dev)[caps]
+    cap_len = _caption_tables(plan, dev, None)[1][caps]
     explained = cap_len <= SGRAF_MAX_WORDS
     w_eff = torch.where(explained, cap_len, torch.zeros_like(cap_len)).to(torch.int64)
     n_eff = torch.where(explained, w_eff + 1, torch.zeros_like(w_eff))
@@ -1736,54 +1762,25 @@ def sgraf_pair_attention(images, words, plan, weights, pairs, module_name='SAF',
                                 aux_ptr if sgr else None, score, cap_len, explained, module_name, sgr_step)
     slot = torch.arange(P, device=dev, dtype=torch.int64)
     if len(plan.len_host) and int(plan.len_host.max()) > SGRAF_MAX_WORDS:
-        lm = ~explained
-        _sgraf_long_caption_pairs(images, words, plan, weights, module_name, sgr_step, S_dim, caps[lm], imgs[lm], slot[lm], score)
-        caps, imgs, slot = caps[~lm], imgs[~lm], slot[~lm]
+        caps, imgs, slot = _long_caption_pairs(images, words, plan, ~explained, caps, imgs, slot, score,
+                                               lambda: _sgraf_long_caption_col(images, weights, module_name, sgr_step, S_dim))
     Ps = caps.numel()
-    SGRAF_ATTN_LAST.update(pairs=Ps, items=0, chunks=0, workspace_bytes=0)
+    SGRAF_ATTN_LAST.update(pairs=Ps, items=0, chunks=0, workspace_bytes=0)      # (reset before the early return, unlike SGRAF_PAIRS_LAST: kept)
     if Ps == 0:
         return result
     # ---- image-major (CSR) form, on the device
-    imgs, order = torch.sort(imgs, stable=True)
-    caps, slot = caps[order], slot[order]
-    img_ptr = torch.zeros(Ni + 1, device=dev, dtype=torch.int32)
-    img_ptr[1:] = torch.cumsum(torch.bincount(imgs, minlength=Ni), 0).to(torch.int32)
+    img_ptr, imgs, caps, slot = _group_pairs(imgs, Ni, (caps, slot), grouped=False)
     pair_img, pair_cap, pair_out = imgs.to(torch.int32), caps.to(torch.int32), slot.to(torch.int32)
-    off, klen = _sgraf_pairs_lens(plan, dev)
-    pair_len, pair_col, pair_capok = (torch.empty(Ps, device=dev, dtype=torch.int32) for _ in range(3))
-    item_begin = torch.empty(Ps + 1, device=dev, dtype=torch.int32)
-    item_img = torch.empty(Ps, device=dev, dtype=torch.int32)
-    n_items_dev = torch.zeros(1, device=dev, dtype=torch.int32)
-    pwb = lib.itr_sgraf_pairs_plan_workspace_bytes(Ni)
-    pws = torch.empty(max(pwb, 1), device=dev, dtype=torch.uint8)
-    _lib.check(lib.itr_sgraf_pairs_plan(_p(img_ptr), _p(pair_cap), _p(off), _p(klen), Ps, Ni, Nc, words.shape[0], _p(pair_len), _p(pair_col),
-                                        _p(pair_capok), _p(item_begin), _p(item_img), _p(n_items_dev), _p(pws), pwb, _stream()))
-    n_items = int(n_items_dev)
-    ib = item_begin[:n_items + 1].cpu().numpy().astype(np.int64)
+    off, klen = _caption_tables(plan, dev, SGRAF_MAX_WORDS)
+    (pair_len, pair_col, pair_capok, item_begin, item_img), n_items, ib = _sgraf_item_plan(lib, img_ptr, pair_cap, off, klen, Ps, Ni, Nc,
+                                                                                          words.shape[0], dev)
     # ---- chunks of whole items sized to the budget
-    if max_workspace_bytes is None:
-        free, _total = torch.cuda.mem_get_info(dev)
-        cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        budget = int(0.9 * (free + cached))
-    else:
-        budget = int(max_workspace_bytes)
+    budget = _workspace_budget(dev, max_workspace_bytes)
 
     def need(it0, it1):
         return lib.itr_sgraf_pair_attention_workspace_bytes(int(ib[it1] - ib[it0]), it1 - it0, D, S_dim, mod, int(sgr_step))
 
-    chunks, it0 = [], 0
-    while it0 < n_items:
-        if need(it0, it0 + 1) > budget:
-            raise torch.cuda.OutOfMemoryError("sgraf_pair_attention: one item needs %d bytes of workspace, %d allowed" % (need(it0, it0 + 1), budget))
-        lo_, hi_ = it0 + 1, n_items                             # the largest it1 whose chunk fits (need is monotone)
-        while lo_ < hi_:
-            mid = (lo_ + hi_ + 1) // 2
-            if need(it0, mid) <= budget:
-                lo_ = mid
-            else:
-                hi_ = mid - 1
-        chunks.append((it0, lo_))
-        it0 = lo_
+    chunks = _chunks_within("sgraf_pair_attention", need, n_items, budget)
     wsb = max(need(a, b) for a, b in chunks)
     ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
     SGRAF_ATTN_LAST.update(items=n_items, chunks=len(chunks), workspace_bytes=int(wsb), budget_bytes=budget)
@@ -1799,61 +1796,29 @@ def sgraf_pair_attention(images, words, plan, weights, pairs, module_name='SAF',
 def sgraf_candidate_attention(images, words, plan, weights, cand, by, m=None, **kw):
     """`sgraf_pair_attention` for candidate lists, `cand` and `by` as in sgraf_candidate_scores: explains the first `m` columns of
     every list (all of them when m is None) -> SgrafPairAttention whose pair q * m + k is list q's entry k."""
-    if by not in ('caption', 'image'):
-        raise ValueError("sgraf_candidate_attention: by must be 'caption' or 'image', got %r" % (by,))
-    cand = _dev(cand, torch.int32, name="cand")
-    if cand.dim() != 2:
-        raise ValueError("sgraf_candidate_attention: cand must be 2-D, got shape %s" % (tuple(cand.shape),))
-    n_q = plan.Nc if by == 'caption' else images.shape[0]
-    if cand.shape[0] != n_q:
-        raise ValueError("sgraf_candidate_attention: by=%r needs %d lists, got %d" % (by, n_q, cand.shape[0]))
-    m = cand.shape[1] if m is None else int(m)
-    if m < 0 or m > cand.shape[1]:
-        raise ValueError("sgraf_candidate_attention: m = %d outside [0, %d]" % (m, cand.shape[1]))
-    flat = cand[:, :m].reshape(-1)
-    qid = torch.arange(n_q, device=cand.device, dtype=torch.int32).repeat_interleave(m)
-    pairs = torch.stack((flat, qid) if by == 'caption' else (qid, flat), 1)
+    _check_by("sgraf_candidate_attention", by)
+    n_q, _, _ = _check_lists("sgraf_candidate_attention", cand, by, images, plan)
+    pairs = _lists_to_pairs("sgraf_candidate_attention", cand.contiguous(), by, n_q, m)
     return sgraf_pair_attention(images, words, plan, weights, pairs, **kw)
 
 
-def _sgraf_long_caption_pairs(images, words, plan, weights, module_name, sgr_step, S_dim, caps, imgs, slot, out):
-    """Listed pairs of captions with 64..191 words: Fusionmodule.encoder_similarity_train(training=False) -- what sgraf_scores runs for
-    such captions -- on each caption's listed images, then a gather into the lists' slots."""
-    if caps.numel() == 0:
-        return
+def _sgraf_long_caption_col(images, weights, module_name, sgr_step, S_dim):
+    """`_long_caption_pairs`' scorer for captions of 64..191 words: Fusionmodule.encoder_similarity_train(training=False) -- what
+    sgraf_scores runs for such captions -- on one caption and its listed images."""
     from .modalmodule import Fusionmodule
-    D = images.shape[2]
-    sim_enc = Fusionmodule.EncoderSimilarity(D, S_dim, module_name, sgr_step)
+    sim_enc = Fusionmodule.EncoderSimilarity(images.shape[2], S_dim, module_name, sgr_step)
     own = sim_enc.state_dict()
     sim_enc.load_state_dict({k: (weights[k].detach() if k in weights else own[k]) for k in own if k in weights or k.endswith('num_batches_tracked')})
     sim_enc.to(images.device).eval()
-    flat = out.view(-1)
-    with torch.no_grad():
-        for c in torch.unique(caps).tolist():
-            m = caps == c
-            sel, inv = torch.unique(imgs[m], return_inverse=True)
-            o, l = int(plan.off_host[c]), int(plan.len_host[c])
-            col = Fusionmodule.encoder_similarity_train(sim_enc, images[sel].contiguous(), words[o:o + l].contiguous(), np.zeros(1, np.int64), [l],
-                                                        None, training=False)
-            flat[slot[m]] = col.reshape(-1)[inv]
+    return lambda im, w, l: Fusionmodule.encoder_similarity_train(sim_enc, im, w, np.zeros(1, np.int64), [l], None, training=False)
 
 
-def _scan_long_caption_pairs(images, words, plan, caps, imgs, slot, out, cross_attn, norm, agg, lambda_lse, lambda_softmax):
-    """Listed pairs of captions with 65..96 words: the one-workgroup-per-pair forward of the training path on each such caption's
-    listed images, then a gather into the lists' slots."""
+def _scan_long_caption_col(cross_attn, norm, agg, lambda_lse, lambda_softmax):
+    """`_long_caption_pairs`' scorer for captions of 65..96 words: the one-workgroup-per-pair forward of the training path on one
+    caption and its listed images."""
     from . import autograd
-    if caps.numel() == 0:
-        return
     fn = autograd.scan_t2i_scores if cross_attn == 't2i' else autograd.scan_i2t_scores
-    flat = out.view(-1)
-    with torch.no_grad():
-        for c in torch.unique(caps).tolist():
-            m = caps == c
-            sel, inv = torch.unique(imgs[m], return_inverse=True)
-            o, l = int(plan.off_host[c]), int(plan.len_host[c])
-            col = fn(images[sel].contiguous(), words[o:o + l].contiguous(), np.zeros(1, np.int64), np.asarray([l], np.int32), norm, agg,
-                     lambda_lse, lambda_softmax)
-            flat[slot[m]] = col.reshape(-1)[inv]
+    return lambda im, w, l: fn(im, w, np.zeros(1, np.int64), np.asarray([l], np.int32), norm, agg, lambda_lse, lambda_softmax)
 
 
 def rerank_lists(idx, val):
