@@ -105,6 +105,10 @@ SIGNATURES = {
     "itr_rank_counts_f64": (i32, [vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp]),
     "itr_rank_t2i_top1_f64": (i32, [vp, i64, i64, i64, i64, vp, vp, vp]),
     "itr_recall_from_ranks": (i32, [vp, i64, vp]),
+    "itr_rank_gt_workspace_bytes": (sz, [i64, i32]),
+    "itr_rank_gt_gather": (i32, [vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "itr_rank_gt_count": (i32, [vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "itr_rank_gt_positions_f64": (i32, [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "itr_topk_workspace_bytes": (sz, [i64, i64, i32]),
     "itr_topk": (i32, [vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, sz, vp]),
     "itr_topk_merge": (i32, [vp, vp, i32, i64, i32, i32, vp, vp, vp]),

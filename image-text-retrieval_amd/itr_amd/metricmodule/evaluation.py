@@ -220,6 +220,93 @@ def cal_recall(sims):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Metrics under ANY ground-truth relation (ops.GroundTruth): several positives per query, or none.
+_GT_SCALARS = ('medr', 'meanr', 'rprecision', 'map_at_r', 'n_queries', 'n_without_positives')
+
+
+def metrics_from_positions(ptr, pos, ks=(1, 5, 10)):
+    """Host numpy, float64.  ptr [n + 1]: CSR pointer of the queries; pos [nnz]: the 0-based position of every positive in its
+    query's ranked list (ops.rank_positions).  Over the queries with at least one positive, R_q their number of positives and
+    p_1 < ... < p_R their positions:
+      r@k        = 100 mean[p_1 < k]
+      medr       = floor(median(p_1)) + 1,  meanr = mean(p_1) + 1          (the reference's formulas, on the best positive)
+      rprecision = 100 mean[#{p_j < R_q} / R_q]
+      map_at_r   = 100 mean[(1 / R_q) sum_{j : p_j < R_q} j / (p_j + 1)]
+    plus n_queries (those with a positive), n_without_positives, and per query (NaN / -1 where it has no positive) the arrays
+    best (p_1), rprecision_q and ap_q."""
+    ptr = np.asarray(ptr, dtype=np.int64)
+    pos = np.asarray(pos, dtype=np.int64)
+    if ptr.ndim != 1 or len(ptr) < 1 or ptr[0] != 0 or ptr[-1] != len(pos) or (np.diff(ptr) < 0).any():
+        raise ValueError("metrics_from_positions: ptr must rise from 0 to len(pos) = %d" % len(pos))
+    R = np.diff(ptr)
+    nq = len(R)
+    has = R > 0
+    n = int(has.sum())
+    seg = np.repeat(np.arange(nq), R)
+    p = pos[np.lexsort((pos, seg))]                      # ascending inside every query
+    j = np.arange(len(p)) - ptr[seg] + 1                 # 1-based index among the query's positives
+    Rq = R[seg].astype(np.float64)
+    hit = p < R[seg]
+    best = np.full(nq, -1, dtype=np.int64)
+    best[has] = p[ptr[:-1][has]]
+    rprec_q = np.full(nq, np.nan)
+    ap_q = np.full(nq, np.nan)
+    rprec_q[has] = (np.bincount(seg, weights=hit / Rq, minlength=nq))[has]
+    ap_q[has] = (np.bincount(seg, weights=np.where(hit, j / (p + 1.0), 0.0) / Rq, minlength=nq))[has]
+    out = OrderedDict()
+    b = best[has]
+    for k in ks:
+        out['r@%d' % k] = 100.0 * int((b < k).sum()) / n if n else float('nan')
+    out['medr'] = float(np.floor(np.median(b)) + 1) if n else float('nan')
+    out['meanr'] = float(int(b.sum())) / n + 1.0 if n else float('nan')
+    out['rprecision'] = 100.0 * float(rprec_q[has].mean()) if n else float('nan')
+    out['map_at_r'] = 100.0 * float(ap_q[has].mean()) if n else float('nan')
+    out['n_queries'] = n
+    out['n_without_positives'] = nq - n
+    out['best'], out['rprecision_q'], out['ap_q'] = best, rprec_q, ap_q
+    return out
+
+
+def gt_metrics(sims, gt, ks=(1, 5, 10)):
+    """`metrics_from_positions` of both directions under the relation `gt` (ops.GroundTruth), the positions counted on the GPU in
+    the arithmetic the caller holds the matrix in (as _ranks: a float64 matrix is ranked in float64).
+    -> {'i2t': {...metrics, 'positions': int64 [nnz] in image-CSR order}, 't2i': {... in caption-CSR order}}."""
+    S = _device_matrix(sims)
+    i_pos, t_pos, _ = ops.rank_positions(S, gt)
+    out = {}
+    for name, ptr, pos in (('i2t', gt.img_ptr_host, i_pos), ('t2i', gt.cap_ptr_host, t_pos)):
+        pos = pos.cpu().numpy().astype(np.int64)
+        out[name] = metrics_from_positions(ptr, pos, ks)
+        out[name]['positions'] = pos
+    return out
+
+
+def _load_gt(path, n_images, n_captions):
+    """`.npz` holding `pairs` [nnz, 2] (image, caption) and optionally n_images / n_captions -> ops.GroundTruth over the gallery."""
+    with np.load(path) as z:
+        if 'pairs' not in z.files:
+            raise ValueError("%s holds no `pairs` array" % path)
+        pairs = z['pairs']
+        for key, have in (('n_images', n_images), ('n_captions', n_captions)):
+            if key in z.files and int(z[key]) != have:
+                raise ValueError("%s: %s = %d, the gallery has %d" % (path, key, int(z[key]), have))
+    return ops.GroundTruth(pairs, n_images, n_captions, torch.device('cuda', torch.cuda.current_device()))
+
+
+def _save_gt(save_dir, data_name, tag, res, gt):
+    import os
+    import yaml
+    scalars = {d: {k: (int(v) if isinstance(v, (int, np.integer)) else float(v)) for k, v in res[d].items() if not isinstance(v, np.ndarray)}
+               for d in ('i2t', 't2i')}
+    scalars['data_name'] = data_name
+    with open(os.path.join(save_dir, f'{data_name}_{tag}_gt_result.yaml'), 'w') as f:
+        yaml.safe_dump(scalars, f)
+    arrays = {f'{d}_{k}': v for d in ('i2t', 't2i') for k, v in res[d].items() if isinstance(v, np.ndarray)}
+    arrays.update(img_ptr=gt.img_ptr_host, cap_ptr=gt.cap_ptr_host, img_cap=gt.img_cap.cpu().numpy(), cap_img=gt.cap_img.cpu().numpy())
+    np.savez(os.path.join(save_dir, f'{data_name}_{tag}_gt_positions.npz'), **arrays)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # evalrank_single / evalrank_ensemble (evaluation.py:262-435): checkpoint -> loader -> encode -> score -> rank ->
 # `<save_dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml`.
 _MEAN_KEYS = ('i2t_r1', 'i2t_r5', 'i2t_r10', 'i2t_medr', 'i2t_meanr', 't2i_r1', 't2i_r5', 't2i_r10', 't2i_medr', 't2i_meanr')
@@ -275,10 +362,11 @@ def _load_for_eval(model_path, data_path):
     return model, _config
 
 
-def _score_blocks(models_embs, fold5, k=0, lists=None):
+def _score_blocks(models_embs, fold5, k=0, lists=None, gt=None):
     """models_embs: list of (model, img_embs, cap_embs, cap_lens, shard_size); the similarity matrices of the
     models are averaged (ensemble, evaluation.py:377-381).  k > 0: the top-k lists of every (float64) matrix go into
-    `lists` (fold5: keys PART_<i>_..., indices local to the part's matrix)."""
+    `lists` (fold5: keys PART_<i>_..., indices local to the part's matrix).  gt: {'path': FILE.npz} (not with fold5): the metrics
+    of that relation on the same matrix go into gt['result'], the relation into gt['relation']."""
     def sims_of(sl_img, sl_cap):
         acc = None
         for model, img, cap, lens, shard in models_embs:
@@ -291,6 +379,9 @@ def _score_blocks(models_embs, fold5, k=0, lists=None):
         sims = sims_of(slice(0, n, 5), slice(None))
         if k > 0:
             lists.update(topk(sims, k))
+        if gt is not None:
+            gt['relation'] = _load_gt(gt['path'], sims.shape[0], sims.shape[1])
+            gt['result'] = gt_metrics(sims, gt['relation'])
         return cal_recall(sims)
     res_dic = {'sum_result': []}
     for i in range(5):
@@ -305,9 +396,12 @@ def _score_blocks(models_embs, fold5, k=0, lists=None):
     return res_dic
 
 
-def _evalrank(model_paths, data_path, split, fold5, tag, topk=0):
+def _evalrank(model_paths, data_path, split, fold5, tag, topk=0, gt=None):
     import os
     import yaml
+    if gt is not None and fold5:
+        raise ValueError("gt does not combine with fold5: a ground-truth relation indexes ONE gallery, fold5 ranks five")
+    gt = None if gt is None else {'path': gt}
     from ..datamodule import data_loader as data
     loaded = [_load_for_eval(p, data_path) for p in model_paths]
     _config = loaded[0][1]
@@ -323,7 +417,7 @@ def _evalrank(model_paths, data_path, split, fold5, tag, topk=0):
         embs.append((model, img, cap, lens, cfg['batch_size'] * 5))
     print('#Images: %d, #Captions: %d' % (embs[0][1].shape[0] / 5, embs[0][2].shape[0]))
     lists = {}
-    res_dic = _score_blocks(embs, fold5, topk, lists)
+    res_dic = _score_blocks(embs, fold5, topk, lists, gt)
     res_dic['data_name'] = _config['data_name'] + ('_5fold' if fold5 else '')
     if len(model_paths) > 1 and fold5:
         res_dic['modal_path_1'], res_dic['modal_path_2'] = model_paths[0], model_paths[1]
@@ -333,6 +427,8 @@ def _evalrank(model_paths, data_path, split, fold5, tag, topk=0):
         yaml.safe_dump(_plain(res_dic), yaml_file)
     if topk > 0:
         _save_topk(save_dir, res_dic['data_name'], tag, topk, lists)
+    if gt is not None:
+        _save_gt(save_dir, res_dic['data_name'], tag, gt['result'], gt['relation'])
     return res_dic
 
 
@@ -386,15 +482,19 @@ def evalrank_fast(model_path, data_path=None, split='dev', fold5=False, comm=Non
     return res_dic
 
 
-def evalrank_single(model_path, data_path=None, split='dev', fold5=False, topk=0):
-    """evaluation.py:262-335.  topk > 0: also `<data_name>[_5fold]_single_top<topk>.npz` next to the YAML (`topk`)."""
-    return _evalrank([model_path], data_path, split, fold5, 'single', topk)
+def evalrank_single(model_path, data_path=None, split='dev', fold5=False, topk=0, gt=None):
+    """evaluation.py:262-335.  topk > 0: also `<data_name>[_5fold]_single_top<topk>.npz` next to the YAML (`topk`).
+    gt: path of an `.npz` holding `pairs` [nnz, 2] (image, caption) and optionally n_images / n_captions, a ground-truth relation
+    over the gallery (not with fold5): besides everything above, `<data_name>_single_gt_result.yaml` gets R@K, medr, meanr,
+    R-Precision and mAP@R of both directions under it and `<data_name>_single_gt_positions.npz` the arrays (`gt_metrics`)."""
+    return _evalrank([model_path], data_path, split, fold5, 'single', topk, gt)
 
 
-def evalrank_ensemble(model_path, model_path2, data_path=None, split='dev', fold5=False, topk=0):
+def evalrank_ensemble(model_path, model_path2, data_path=None, split='dev', fold5=False, topk=0, gt=None):
     """evaluation.py:338-435: the two models' similarity matrices are averaged before ranking.  topk > 0: the top-k lists
-    of the float64 average go to `<data_name>[_5fold]_ensemble_top<topk>.npz`."""
-    return _evalrank([model_path, model_path2], data_path, split, fold5, 'ensemble', topk)
+    of the float64 average go to `<data_name>[_5fold]_ensemble_top<topk>.npz`.  gt: as evalrank_single, on the float64 average
+    -> `<data_name>_ensemble_gt_result.yaml` / `..._ensemble_gt_positions.npz`."""
+    return _evalrank([model_path, model_path2], data_path, split, fold5, 'ensemble', topk, gt)
 
 
 # ---------------------------------------------------------------------------------------------------------

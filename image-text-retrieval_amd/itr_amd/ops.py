@@ -1048,6 +1048,156 @@ def recall_from_ranks(ranks):
     return tuple(float(v) for v in out)
 
 
+# ------------------------------------------------------------------------------------------ any ground-truth relation
+def ground_truth_csr(pairs, n_images, n_captions):
+    """Host side of `GroundTruth`: integer [nnz, 2] (image, caption) pairs -> (img_ptr [Ni + 1], img_cap [nnz], cap_ptr [Nc + 1],
+    cap_img [nnz]) int32 numpy arrays, the relation by image (captions ascending) and by caption (images ascending).
+    An index out of range or a pair given twice raises ValueError naming the pair: nothing unchecked reaches a kernel."""
+    n_images, n_captions = int(n_images), int(n_captions)
+    if n_images < 0 or n_captions < 0:
+        raise ValueError("GroundTruth: negative gallery size (%d images, %d captions)" % (n_images, n_captions))
+    p = pairs.detach().cpu().numpy() if torch.is_tensor(pairs) else np.asarray(pairs)
+    if p.size == 0:
+        p = np.zeros((0, 2), dtype=np.int64)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError("GroundTruth: pairs must have shape [nnz, 2] (image, caption), got %s" % (tuple(p.shape),))
+    if not np.issubdtype(p.dtype, np.integer):
+        raise TypeError("GroundTruth: pairs must be integers, got %s" % p.dtype)
+    p = p.astype(np.int64, copy=False)
+    nnz = p.shape[0]
+    if nnz >= 2 ** 31 - 1 or n_images >= 2 ** 31 - 1 or n_captions >= 2 ** 31 - 1:
+        raise NotImplementedError("GroundTruth: nnz, n_images and n_captions must be below 2^31")
+    img, cap = p[:, 0], p[:, 1]
+    bad = np.flatnonzero((img < 0) | (img >= n_images) | (cap < 0) | (cap >= n_captions))
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError("GroundTruth: pair %d = (image %d, caption %d) is out of range for %d images x %d captions"
+                         % (b, int(img[b]), int(cap[b]), n_images, n_captions))
+    by_img = np.lexsort((cap, img))
+    key = img[by_img] * max(n_captions, 1) + cap[by_img]
+    dup = np.flatnonzero(key[1:] == key[:-1])
+    if dup.size:
+        b = int(by_img[dup[0] + 1])
+        raise ValueError("GroundTruth: pair %d = (image %d, caption %d) is given more than once" % (b, int(img[b]), int(cap[b])))
+    by_cap = np.lexsort((img, cap))
+
+    def ptr(idx, n):
+        out = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(idx, minlength=n), out=out[1:])
+        return out.astype(np.int32)
+    return ptr(img, n_images), cap[by_img].astype(np.int32), ptr(cap, n_captions), img[by_cap].astype(np.int32)
+
+
+class GroundTruth:
+    """A ground-truth relation between n_images images and n_captions captions for `rank_positions`: any number of positives per
+    query.  pairs: integer [nnz, 2] (image, caption), numpy or tensor, validated on the host (`ground_truth_csr`), then both CSR
+    forms are uploaded once.  Attributes: img_ptr / img_cap / cap_ptr / cap_img (int32 device tensors), nnz, n_images, n_captions,
+    device, and the host copies img_ptr_host / cap_ptr_host."""
+
+    def __init__(self, pairs, n_images, n_captions, device):
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError("GroundTruth on %s: the itr_amd ops only run on the GPU (no CPU fallback)" % device)
+        ip, ic, cp, ci = ground_truth_csr(pairs, n_images, n_captions)
+        self.n_images, self.n_captions, self.nnz, self.device = int(n_images), int(n_captions), int(ic.shape[0]), device
+        self.img_ptr_host, self.cap_ptr_host = ip, cp
+        self.img_ptr, self.img_cap, self.cap_ptr, self.cap_img = (
+            h2d(a, device) if a.size else torch.zeros(0, device=device, dtype=torch.int32) for a in (ip, ic, cp, ci))
+
+    @classmethod
+    def from_layout(cls, n_images, n_captions, im_div, device):
+        """The relation of the reference's layout: caption j belongs to image j // im_div (captions past the last image: to none)."""
+        if int(im_div) < 1:
+            raise ValueError("GroundTruth.from_layout: im_div must be >= 1, got %r" % (im_div,))
+        cap = np.arange(int(n_captions), dtype=np.int64)
+        img = cap // int(im_div)
+        keep = img < int(n_images)
+        return cls(np.stack([img[keep], cap[keep]], 1), n_images, n_captions, device)
+
+
+class RankPositionsState:
+    """Keys and accumulators of a row-block sweep (`rank_gather_keys`, then `rank_positions`): uint64-as-int64 [nnz] keys of both
+    orders, int32 [nnz] positions."""
+
+    def __init__(self, gt):
+        z = lambda dt: torch.zeros(gt.nnz, device=gt.device, dtype=dt)       # noqa: E731
+        self.gt = gt
+        self.i2t_key, self.t2i_key, self.i2t_pos, self.t2i_pos = z(torch.int64), z(torch.int64), z(torch.int32), z(torch.int32)
+
+
+def _rank_gt_block(who, S, gt, row0, state):
+    if not isinstance(gt, GroundTruth):
+        raise TypeError("%s: gt must be an ops.GroundTruth" % who)
+    if not torch.is_tensor(S):
+        raise TypeError("S must be a torch tensor")
+    if S.dim() != 2:
+        raise ValueError("%s: S must be 2-D, got shape %s" % (who, tuple(S.shape)))
+    if S.dtype not in (torch.float32, torch.float64):
+        raise TypeError("S must be torch.float32 or torch.float64, got %s" % S.dtype)
+    S_ = _dev_view(S, S.dtype)
+    if S_.device != gt.device:
+        raise ValueError("%s: S is on %s, the relation on %s" % (who, S_.device, gt.device))
+    row0 = int(row0)
+    n, Nc = S_.shape
+    if Nc != gt.n_captions or row0 < 0 or row0 + n > gt.n_images:
+        raise ValueError("%s: S holds rows %d .. %d of %d columns, the relation is over %d images x %d captions"
+                         % (who, row0, row0 + n - 1, Nc, gt.n_images, gt.n_captions))
+    if state is not None and not (isinstance(state, RankPositionsState) and state.gt is gt):
+        raise ValueError("%s: state must be the RankPositionsState of this relation's sweep" % who)
+    if S_.dtype == torch.float64 and (state is not None or row0 != 0 or n != gt.n_images):
+        raise ValueError("%s: a float64 matrix is ranked whole (row0 = 0, every row, no state)" % who)
+    return S_, row0, n, Nc
+
+
+def rank_gather_keys(S_block, gt, row0=0, state=None):
+    """First sweep over the row blocks of a matrix: the order keys of the positives whose row lies in this block (fp32 [n, Nc]
+    holding global rows row0 .. row0 + n - 1; any row stride and alignment) go into `state` (None: a new one) -> state.  A
+    caption's positives may lie in other blocks' rows, so every block is gathered before the first is counted."""
+    lib = _lib.load()
+    S_, row0, n, Nc = _rank_gt_block("rank_gather_keys", S_block, gt, row0, state)
+    if S_.dtype == torch.float64:
+        raise ValueError("rank_gather_keys: a float64 matrix is ranked whole by rank_positions")
+    if state is None:
+        state = RankPositionsState(gt)
+    if gt.nnz and n and Nc:
+        _lib.check(lib.itr_rank_gt_gather(_p(S_), S_.stride(0), row0, n, Nc, gt.n_images, gt.nnz, _p(gt.img_ptr), _p(gt.img_cap), _p(gt.cap_ptr),
+                                          _p(gt.cap_img), _p(state.i2t_key), _p(state.t2i_key), _stream()))
+    return state
+
+
+def rank_positions(S, gt, row0=0, state=None):
+    """Where do the positives of `gt` rank?  -> (i2t_pos int32 [nnz] in image-CSR order, t2i_pos int32 [nnz] in caption-CSR order,
+    state): the 0-based position of every positive in its query's ranked list, in the ranker's order (larger score first, the
+    higher index on an exact tie, -0.0 == +0.0, NaN as +inf) -- counted, not sorted (csrc/rank_gt.hip).
+    Whole matrix (row0 = 0, every row, state None): one call gathers and counts; both outputs are final.  float64 matrices are
+    ranked in float64 and only whole.
+    Row blocks (fp32): sweep `rank_gather_keys` over the blocks, then this function with the same state; after the last block both
+    outputs (state.i2t_pos / state.t2i_pos, returned by every call) are final, whatever the partition and the order."""
+    lib = _lib.load()
+    S_, row0, n, Nc = _rank_gt_block("rank_positions", S, gt, row0, state)
+    whole = state is None
+    if whole and not (row0 == 0 and n == gt.n_images):
+        raise ValueError("rank_positions: without a state S must be the whole matrix (%d rows from row 0), got %d rows from row %d; "
+                         "row blocks are gathered first (rank_gather_keys)" % (gt.n_images, n, row0))
+    if whole:
+        state = RankPositionsState(gt)
+    if not (gt.nnz and n and Nc):
+        return state.i2t_pos, state.t2i_pos, state
+    f64 = S_.dtype == torch.float64
+    wsb = lib.itr_rank_gt_workspace_bytes(gt.nnz, 1 if f64 else 0)
+    ws = torch.empty(wsb // 8 + 1, device=gt.device, dtype=torch.int64)
+    if f64:
+        _lib.check(lib.itr_rank_gt_positions_f64(_p(S_), S_.stride(0), n, Nc, gt.nnz, _p(gt.img_ptr), _p(gt.img_cap), _p(gt.cap_ptr),
+                                                 _p(gt.cap_img), _p(state.i2t_pos), _p(state.t2i_pos), _p(ws), wsb, _stream()))
+        return state.i2t_pos, state.t2i_pos, state
+    if whole:
+        _lib.check(lib.itr_rank_gt_gather(_p(S_), S_.stride(0), 0, n, Nc, gt.n_images, gt.nnz, _p(gt.img_ptr), _p(gt.img_cap), _p(gt.cap_ptr),
+                                          _p(gt.cap_img), _p(state.i2t_key), _p(state.t2i_key), _stream()))
+    _lib.check(lib.itr_rank_gt_count(_p(S_), S_.stride(0), row0, n, Nc, gt.n_images, gt.nnz, _p(gt.img_ptr), _p(gt.cap_ptr), _p(state.i2t_key),
+                                     _p(state.t2i_key), _p(state.i2t_pos), _p(state.t2i_pos), 1 if whole else 0, _p(ws), wsb, _stream()))
+    return state.i2t_pos, state.t2i_pos, state
+
+
 # ------------------------------------------------------------------------------------------
 TOPK_MAX = 128         # ITR_TOPK_MAX (include/itr_hip.h)
 TOPK_MAX_PARTS = 32    # ITR_TOPK_MAX_PARTS

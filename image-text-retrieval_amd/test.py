@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Evaluate checkpoints like the reference's test.py:  python test.py MODEL_PATH [MODEL_PATH_2] [--data-path P]
-[--split test|testall|dev] [--fold5] [--topk K] [--rerank K [--stream-coarse] [--explain M | --explain-sgraf M]]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
+[--split test|testall|dev] [--fold5] [--topk K] [--gt FILE.npz] [--rerank K [--stream-coarse] [--explain M | --explain-sgraf M]]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
 (and with --topk K the top-K retrieval lists of every query in <data_name>[_5fold]_{single,ensemble}_top<K>.npz).
+With --gt FILE.npz (`pairs` [nnz, 2] of (image, caption), optionally n_images / n_captions): a ground-truth relation with any number of
+positives per query  ->  also <data_name>_{single,ensemble}_gt_result.yaml (R@K, medr, meanr, R-Precision, mAP@R of both directions)
+and <data_name>_{single,ensemble}_gt_positions.npz (the position of every positive in its query's ranked list)
 python test.py COARSE_PATH FINE_PATH --rerank K: coarse-to-fine retrieval, the first model shortlists K candidates per query and the
 second (SCAN or SGRAF) scores only those  ->  <data_name>[_5fold]_rerank<K>_result.yaml and <data_name>[_5fold]_rerank<K>.npz
 With --explain M (SCAN fine model): also the word-by-region attention maps, per-word / per-region similarities and scores of the
@@ -29,6 +32,9 @@ if __name__ == "__main__":
                     help="sharded device-resident evaluation (evalpipe.evaluate_precomp); run under torch.distributed.run for >1 GPU")
     ap.add_argument("--topk", type=int, default=0, metavar="K",
                     help="also write the top-K retrieved items of every query (indices and scores) to <data_name>..._top<K>.npz")
+    ap.add_argument("--gt", default=None, metavar="FILE.npz",
+                    help="a ground-truth relation over the gallery (`pairs` [nnz, 2] of (image, caption)): also write R@K, R-Precision and "
+                         "mAP@R under it to <data_name>_..._gt_result.yaml and every positive's position to ..._gt_positions.npz")
     ap.add_argument("--rerank", type=int, default=0, metavar="K",
                     help="two checkpoints COARSE FINE: FINE (SCAN or SGRAF) re-scores only COARSE's top-K candidates of every query; "
                          "three to five checkpoints COARSE FINE_1 FINE_2 [FINE_3 [FINE_4]]: the fine models' scores of those candidates "
@@ -48,6 +54,13 @@ if __name__ == "__main__":
         ap.error("--explain needs --rerank K")
     if a.explain_sgraf is not None and not a.rerank:
         ap.error("--explain-sgraf needs --rerank K")
+    if a.gt is not None and a.rerank:
+        ap.error("--gt does not combine with --rerank: metrics of reranked lists under a general relation are not implemented")
+    if a.gt is not None and a.fast:
+        ap.error("--gt does not combine with --fast: the sharded evaluation ranks the 5-captions-per-image layout only")
+    if a.gt is not None and a.fold5:
+        ap.error("--gt does not combine with --fold5: a relation indexes one gallery")
+    gt_kw = {} if a.gt is None else {'gt': a.gt}
     if a.rerank:
         if not 2 <= len(a.model_path) <= 5:
             ap.error("--rerank needs two checkpoints, COARSE FINE, or for an ensemble up to five: COARSE FINE_1 FINE_2 [FINE_3 [FINE_4]]")
@@ -70,7 +83,7 @@ if __name__ == "__main__":
         if dist.is_initialized():
             dist.destroy_process_group()
     elif len(a.model_path) == 1:
-        evaluation.evalrank_single(a.model_path[0], data_path=a.data_path, split=a.split, fold5=a.fold5, topk=a.topk)
+        evaluation.evalrank_single(a.model_path[0], data_path=a.data_path, split=a.split, fold5=a.fold5, topk=a.topk, **gt_kw)
     else:
         evaluation.evalrank_ensemble(a.model_path[0], a.model_path[1], data_path=a.data_path, split=a.split, fold5=a.fold5,
-                                     topk=a.topk)
+                                     topk=a.topk, **gt_kw)

@@ -368,6 +368,37 @@ int itr_rank_t2i_top1_f64(const double *S, int64_t ldS, int64_t row0, int64_t n_
 /* host-side summary (evaluation.py:181-185): out5 = r1, r5, r10, medr, meanr. */
 int itr_recall_from_ranks(const int32_t *ranks_host, int64_t n, double *out5);
 
+/* ---- positions under any ground-truth relation (csrc/rank_gt.hip) -------------------------
+ * The ranker above knows one ground truth, caption j <-> image j / im_div.  These entry points take a sparse relation in both
+ * CSR forms (int32, on the device): img_ptr [Ni + 1] / img_cap [nnz], the positive captions of every image, ascending within an
+ * image, and cap_ptr [Nc + 1] / cap_img [nnz], the positive images of every caption, ascending.  They return, per pair,
+ *   i2t_pos [nnz] (image-CSR order) / t2i_pos [nnz] (caption-CSR order): the 0-based position of that positive in its query's
+ *   ranked list = #{k : key_k > key_positive} over the whole row / column, in the ranker's order (larger score first, the higher
+ *   index on an exact tie, -0.0 == +0.0, NaN as +inf).  Any number of positives per query, from none to the whole gallery.
+ * S [n_rows_local, Nc] is a row block holding global rows row0 .. row0 + n_rows_local - 1 of the Ni rows (ldS >= Nc, any alignment).
+ *   itr_rank_gt_gather writes the keys of the positives whose ROW lies in the block into i2t_key / t2i_key [nnz] (uint64; other
+ *     entries are left untouched): a column's positives may lie in rows of another block, so all blocks are gathered first;
+ *   itr_rank_gt_count counts the block against the keys: i2t_pos of the block's rows is final (plain stores), t2i_pos is an
+ *     integer sum over row blocks (other blocks, other ranks just add).  flags: ITR_RANK_GT_INIT = zero t2i_pos inside the call
+ *     (the first block, or a whole matrix).  workspace: itr_rank_gt_workspace_bytes(nnz, 0) bytes, 8-byte aligned.
+ * itr_rank_gt_positions_f64: a whole float64 matrix (cal_sims' output, ensemble averages) in float64 order (ordered double, then
+ * the index), gather and count in one call; workspace: itr_rank_gt_workspace_bytes(nnz, 1) bytes.
+ * The relation must be well formed (the Python layer validates it on the host); whatever it holds, no entry of it becomes an
+ * address unchecked.  Null pointers, ldS < Nc, negative sizes, rows past Ni -> ITR_ERR_BADARG; nnz, Ni or Nc >= 2^31 ->
+ * ITR_ERR_UNSUPPORTED; nnz == 0, n_rows_local == 0 or Nc == 0 -> ITR_OK, nothing written.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+#define ITR_RANK_GT_INIT 1
+size_t itr_rank_gt_workspace_bytes(int64_t nnz, int f64);
+int itr_rank_gt_gather(const float *S, int64_t ldS, int64_t row0, int64_t n_rows_local, int64_t Nc, int64_t Ni, int64_t nnz,
+                       const int32_t *img_ptr, const int32_t *img_cap, const int32_t *cap_ptr, const int32_t *cap_img,
+                       uint64_t *i2t_key, uint64_t *t2i_key, itr_stream_t stream);
+int itr_rank_gt_count(const float *S, int64_t ldS, int64_t row0, int64_t n_rows_local, int64_t Nc, int64_t Ni, int64_t nnz,
+                      const int32_t *img_ptr, const int32_t *cap_ptr, const uint64_t *i2t_key, const uint64_t *t2i_key,
+                      int32_t *i2t_pos, int32_t *t2i_pos, int flags, void *workspace, size_t workspace_bytes, itr_stream_t stream);
+int itr_rank_gt_positions_f64(const double *S, int64_t ldS, int64_t Ni, int64_t Nc, int64_t nnz, const int32_t *img_ptr,
+                              const int32_t *img_cap, const int32_t *cap_ptr, const int32_t *cap_img, int32_t *i2t_pos,
+                              int32_t *t2i_pos, void *workspace, size_t workspace_bytes, itr_stream_t stream);
+
 /* ---- top-K retrieval lists (itr/metricmodule/evaluation.py:156-222) ----------------------
  * The reference builds the full ranked list of every query, inds = np.argsort(sims[index])[::-1] (evaluation.py:169 i2t,
  * :209 t2i), and keeps inds[0] and the ground truth's position.  These entry points return the first K entries of those
