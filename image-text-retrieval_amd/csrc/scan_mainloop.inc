@@ -55,8 +55,10 @@
     // tools/audit_asm_loads.py).  So the whole loop -- prologue, K loop, peeled tail, park -- is ONE asm statement with
     // hand-allocated registers (generated: tools/gen_scan_mainloop.py; v[64:235], s[80:86] are listed as clobbered, hipcc
     // keeps its values elsewhere), nothing is in flight when it ends, and the MFMA / memory interleave is the one written
-    // there (one memory instruction behind each of the first MFMAs of a half chunk: tools/ubench/mfma_pipe, 3091 -> 2686
-    // cycles per chunk against issuing them in a clump).
+    // there: one memory instruction behind each of the first MFMAs of a half chunk, the 7 park stores behind every OTHER
+    // one, with the fragment reads between them.  tools/ubench/mfma_pipe: 3091 cycles per chunk issued in a clump, 2456 with
+    // the 7 stores behind 7 consecutive MFMAs (the four waves' 16-byte LDS stores, ~13 LDS cycles each, then outrun the LDS
+    // and stall MFMA issue when a wave has no partner on its SIMD), 2358 as it is now, against 2304 of pure MFMA issue.
     const unsigned park_addr = lds0 + (unsigned)(((wave * 16 + fi) * SC_LDT + fg * 4) * 4);   // &sm.arawt[wave*16 + fi][fg*4]
     if (nk >= 3) {
         const char *bbase2 = bbase + bpass;
