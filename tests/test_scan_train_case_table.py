@@ -1,0 +1,224 @@
+"""No GPU: the case table of the SCAN training sweep (tests/helpers/scan_train_cases.py) is fit for its purpose.
+
+Coverage: every seam value of the launch code keeps a case, every outcome of the three routing mirrors is reached, and every pair
+kernel instantiation of both directions meets every first norm and every aggregation.  References: the float64 mirror of the
+kernels' algebra is the oracle's function (1e-11), so its float32 run measures that algebra's own rounding.  Conditioning: every
+compared tensor's bound is at most 2^-10 of its largest value.  Sensitivity: each claimed defect moves its tensor by at least 10 x
+the bound the GPU sweep applies.  Pins: the constants and gates the mirrors copy are checked against the source text of csrc/ and
+autograd.py, so an edit to the kernels' geometry fails here instead of silently moving the seams."""
+import os
+import re
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import scan_train_cases as S        # noqa: E402
+import train_prim_cases as P        # noqa: E402
+
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "image-text-retrieval_amd")
+
+
+def _seen(xa, param):
+    out = set()
+    for c in S.cases(xa):
+        out |= set(str(v) for v in c.seams().get(param, ()))
+    return out
+
+
+@pytest.mark.parametrize("xa", S.DIRECTIONS)
+def test_every_seam_value_has_a_case(xa):
+    assert S.cases(xa)
+    for param, values in S.SEAMS[xa].items():
+        missing = [v for v in values if str(v) not in _seen(xa, param)]
+        assert not missing, "%s: no case with %s in %s" % (xa, param, missing)
+
+
+def test_seam_lists_are_the_ones_of_the_launch_code():
+    t, i = S.SEAMS['t2i'], S.SEAMS['i2t']
+    assert set(t['R']) >= {1, 16, 17, 35, 36, 37, 48, 49, 100}
+    assert set(t['max_len@R=36']) >= {1, 32, 33, 64, 65, 96} and set(t['max_len@R<36']) >= {64, 65, 96}
+    assert set(t['max_len@R>36,backward']) >= {64} and set(t['max_len@R>36,forward only']) >= {65, 96}
+    assert set(t['R*W']) == {'<256', '=256', '>256'}
+    assert set(i['R']) >= {1, 35, 36, 37, 100} and set(i['W']) >= {1, 2, 16, 17, 64, 65, 96} and (100, 96) in set(i['R,W'])
+    assert set(i['W*W']) >= {256, 289}
+    for d in (t, i):
+        assert set(d['D']) >= {1, 31, 32, 33, 62, 63, 64, 65, 255, 256, 257, 513}
+        assert any(v % 4 for v in d['D']) and any(v > 256 for v in d['D'])
+        assert set(d['Bc']) >= {1, 15, 16, 17, 33} and set(d['Bi']) >= {1, 2, 5} and set(d['n_tok']) >= {31, 32, 33}
+        assert any(v for v in d['n_tok%4']) and set(d['unaligned']) == {0, 1} and set(d['ntp']) >= {32, 64}
+    assert any(v for v in i['Bi*R%4'])
+    assert set(t['gram_route']) == {'mfma', 'gram36', 'train_gram'} and set(t['dg_reduce_blocks']) >= {1, 2} and set(t['R*R']) >= {256, 289}
+    assert set(t['gram_route@R,D%4,aligned']) >= {(36, 0, 1), (36, 1, 0), (48, 1, 1), (49, 1, 1)}
+    assert len(t['fwd_route']) == 7 and len(t['bwd_route']) == 7 and 'rejected' in t['bwd_route'] and len(i['fwd_route']) == 3
+    assert len(S.CASES) <= 300 and len(set(c.name for c in S.CASES)) == len(S.CASES)
+
+
+def test_table_shapes_follow_the_rules():
+    for c in S.CASES:
+        assert all(w >= 1 for w in c.lens) and c.n_tok == sum(c.lens)
+        if c.group == 'pair' and c.max_len > 2:         # captions of 1 and 2 words ride in the same batch
+            assert 1 in c.lens and 2 in c.lens, c
+        if c.D > 256:
+            assert c.Bi <= 2, c
+    assert any(list(c.lens) != sorted(c.lens, reverse=True) and list(c.lens) != sorted(c.lens) for c in S.CASES)
+    # a case without a backward is one the library rejects, nothing else
+    for c in S.CASES:
+        assert c.backward == (not (c.xa == 't2i' and c.R > S.SC_R and c.max_len > 64)), c
+
+
+def test_routing_mirrors():
+    assert S.t2i_pair_route(36, 32, False) == (32, 36, True) and S.t2i_pair_route(36, 33, True) == (64, 36, True)
+    assert S.t2i_pair_route(36, 64, True) == (64, 36, True) and S.t2i_pair_route(36, 65, True) == (96, 36, True)
+    assert S.t2i_pair_route(35, 32, False) == (64, 36, False) and S.t2i_pair_route(1, 96, True) == (96, 36, False)
+    assert S.t2i_pair_route(37, 64, True) == (64, 100, False) and S.t2i_pair_route(37, 65, False) == (96, 100, False)
+    assert S.t2i_pair_route(37, 65, True) == 'rejected' and S.t2i_pair_route(101, 1, False) == 'rejected'
+    assert S.t2i_pair_route(36, 97, False) == 'rejected' and S.t2i_pair_route(0, 1, False) == 'rejected'
+    assert [S.i2t_pair_route(r) for r in (1, 35, 36, 37, 100, 101)] == [(36, False), (36, False), (36, True), (100, False), (100, False), 'rejected']
+    assert S.i2t_pair_route(36, 97) == 'rejected'
+    assert S.gram_route(36, 16, True) == 'mfma' and S.gram_route(36, 18, True) == 'gram36' and S.gram_route(36, 16, False) == 'gram36'
+    assert S.gram_route(48, 16, True) == 'mfma' and S.gram_route(49, 16, True) == 'train_gram' and S.gram_route(48, 16, False) == 'train_gram'
+    assert [S.dg_reduce_blocks(r) for r in (1, 16, 17, 36, 100)] == [1, 1, 2, 6, 40]
+    assert [S.ntp(n) for n in (1, 31, 32, 33, 64, 65)] == [32, 32, 32, 64, 64, 96]
+
+
+@pytest.mark.parametrize("xa", S.DIRECTIONS)
+def test_every_instantiation_meets_every_norm_and_aggregation(xa):
+    cs = S.cases(xa)
+    fwd = set(S.T2I_ROUTES) if xa == 't2i' else set(S.I2T_ROUTES)
+    bwd = fwd - {(S.ST_MAXW, S.ST_RMAX, False)} if xa == 't2i' else fwd
+    assert set(c.fwd_route for c in cs) == fwd and set(c.bwd_route for c in cs if c.backward) == bwd
+    for which, routes in (('fwd_route', fwd), ('bwd_route', bwd)):
+        have_n = set((getattr(c, which), c.norm) for c in cs)
+        have_a = set((getattr(c, which), c.agg) for c in cs)
+        for r in routes:
+            assert not [n for n in S.NORMS if (r, n) not in have_n], (which, r)
+            assert not [a for a in S.AGGS if (r, a) not in have_a], (which, r)
+    # the rotation outside the pair groups brings every norm together with every aggregation
+    assert set((c.norm, c.agg) for c in cs) == set((n, a) for n in S.NORMS for a in S.AGGS)
+    if xa == 't2i':         # every Gram route and both dG reduce grids run a backward
+        assert set(S.gram_route(c.R, c.D, not c.unaligned) for c in cs if c.backward) == {'mfma', 'gram36', 'train_gram'}
+        assert set(S.dg_reduce_blocks(c.R) for c in cs if c.group == 'Bc') == {1, 2}
+        assert set(c.Bc for c in cs if c.group == 'Bc' and c.R == 16) == set(c.Bc for c in cs if c.group == 'Bc' and c.R == 17) == set(S.SCAN_BC)
+        for D in (257, 513):            # the three region classes of scan_train_gram_bwd_kernel with a second workgroup along D
+            assert set(c.bwd_route[1:] for c in cs if c.D == D) == {(36, True), (36, False), (100, False)}
+    else:
+        assert any(c.R == 100 and 96 in c.lens and c.backward for c in cs)
+        assert any(c.D in (1, 31, 33, 63) and 17 in c.lens and 16 in c.lens for c in cs)
+
+
+@pytest.mark.parametrize("xa", S.DIRECTIONS)
+def test_mirror_is_the_oracles_function_and_its_float32_run_is_inside_the_bound(xa):
+    for c in S.cases(xa):
+        ref = c.reference()
+        assert set(ref) == ({'S', 'd_images', 'd_words'} if c.backward else {'S'}), c
+        for name, (want, e_oracle, e_mirror, tol, agree) in ref.items():
+            assert bool(torch.isfinite(want).all()) and e_oracle == e_oracle and e_mirror == e_mirror, (c, name)
+            assert agree <= S.MIRROR_AGREES * max(1.0, float(want.abs().max())), (c, name, agree)
+            if c.name not in S.FALLBACK:
+                assert tol == S.FACTOR * max(e_oracle, e_mirror, S.U * float(want.abs().max())), (c, name)
+                assert e_mirror <= tol / S.FACTOR and e_oracle <= tol / S.FACTOR, (c, name)
+        if c.backward:
+            assert ref['d_words'][0].shape == (c.n_tok, c.D) and ref['d_images'][0].shape == (c.Bi, c.R, c.D)
+        assert ref['S'][0].shape == (c.Bi, c.Bc)
+
+
+@pytest.mark.parametrize("xa", S.DIRECTIONS)
+def test_conditioning_cap(xa):
+    exempt = 0
+    for c in S.cases(xa):
+        for name, (want, e_oracle, e_mirror, tol, _) in c.reference().items():
+            m = float(want.abs().max())
+            if c.capped(name):
+                assert tol <= S.CAP * m, "%s %s: tol %.3g is %.3g of max|want| %.3g (e32 oracle %.3g, mirror %.3g)" % (
+                    c, name, tol, tol / m, m, e_oracle, e_mirror)
+            else:       # D = 1: the gradient is zero in exact arithmetic
+                assert c.D == S.CAP_EXEMPT_D == 1 and name != 'S' and m <= 1e-9, (c, name, m)
+                exempt += 1
+    assert exempt == 2 * len([c for c in S.cases(xa) if c.D == 1]) == 2
+
+
+@pytest.mark.parametrize("xa", S.DIRECTIONS)
+def test_bound_sees_every_claimed_defect(xa):
+    claimed = {}
+    for c in S.cases(xa):
+        want_claims = 'a' + ('' if c.D == 1 else ('b' if c.R > 1 else '') + ('c' if c.max_len > 1 else '') +
+                             ('d' if c.backward and c.Bc > 1 else '') + ('e' if c.backward and c.Bi > 1 else ''))
+        assert c.claims == want_claims, c
+        ref = c.reference()
+        for letter, (name, value) in c.defects().items():
+            want, _, _, tol, _ = ref[name]
+            assert value.shape == want.shape, (c, letter)
+            moved = float((value - want).abs().max())
+            assert moved >= S.SENSITIVITY * tol, "%s defect %s moves %s by %.3g, %.3g x its bound" % (c, letter, name, moved, moved / tol)
+            claimed.setdefault(letter, []).append(c)
+    assert set(claimed) == set('abcde')
+    # Max: the dropped element carries the maximum (the tie of tests/helpers/scan_train_cases.py)
+    assert any(c.agg == 'Max' and c.tied for c in claimed['b']) and any(c.agg == 'Max' and c.tied for c in claimed['c'])
+    assert all(c.tied for c in S.cases(xa) if c.agg == 'Max') and not any(c.tied for c in S.cases(xa) if c.agg != 'Max')
+
+
+def test_fallback_list():
+    assert set(S.FALLBACK) <= set(c.name for c in S.CASES)
+    assert len(S.FALLBACK) <= S.FALLBACK_SHARE * len(S.CASES)
+    assert S.FALLBACK_SHARE == 0.02 and S.FACTOR == P.FACTOR == 16 and S.U == P.U == 2.0 ** -24 and S.SENSITIVITY == P.SENSITIVITY == 10
+    assert S.CAP == 2.0 ** -10 and S.MIRROR_AGREES == 1e-11 and (S.LAMBDA_LSE, S.LAMBDA_SOFTMAX) == (6.0, 9.0)
+
+
+def _src(*path):
+    with open(os.path.join(PKG, *path)) as f:
+        return re.sub(r"\s+", " ", f.read())
+
+
+def test_constants_are_the_ones_of_the_source():
+    """The mirrors' constants and gates, as the source text states them (whitespace folded)."""
+    text = {"scan_train.hip": _src("csrc", "scan_train.hip"), "scan_train_i2t.hip": _src("csrc", "scan_train_i2t.hip"),
+            "scan_common.h": _src("csrc", "scan_common.h"), "autograd.py": _src("itr_amd", "autograd.py"), "ops.py": _src("itr_amd", "ops.py")}
+    pins = {
+        "scan_common.h": ("constexpr int SC_R = %d;" % S.SC_R,),
+        "scan_train.hip": (
+            "constexpr int ST_RMAX = %d;" % S.ST_RMAX, "constexpr int ST_MAXW = %d;" % S.ST_MAXW,
+            # check_train_args and the two launchers
+            "ITR_UNSUPPORTED(R < 1 || R > ST_RMAX,", "ITR_UNSUPPORTED(max_len > ST_MAXW,",
+            "const bool w64 = max_len <= 64;",
+            "if (R == SC_R && max_len <= 32) return launch_pair<PairSmem<32, SC_R>>(scan_train_fwd_kernel<32, SC_R, true>,",
+            "if (R == SC_R && max_len <= 32) return launch_pair<PairBwdSmem<32, SC_R>>(scan_train_bwd_dense_kernel<32, SC_R, true>,",
+            ": launch_pair<PairSmem<ST_MAXW, ST_RMAX>>(scan_train_fwd_kernel<ST_MAXW, ST_RMAX, false>,",
+            "return launch_pair<PairBwdSmem<64, ST_RMAX>>(scan_train_bwd_kernel<64, ST_RMAX, false>,",
+            "ITR_UNSUPPORTED(R > SC_R && max_len > 64,",
+            # itr_scan_train_prepare
+            "if (R <= %d && D %% 4 == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0)" % S.GRAM_MFMA_RMAX,
+            "else if (R == SC_R) hipLaunchKernelGGL(gram_kernel,",
+            "hipLaunchKernelGGL(rownorm_train_kernel, dim3((unsigned)ceil_div(n_tok, 4)), dim3(256),",
+            # the dG reduce and the finishing grids
+            "for (; c + %d <= Bc; c += %d) {" % (S.DG_UNROLL, S.DG_UNROLL), "float v[%d];" % S.DG_UNROLL,
+            "hipLaunchKernelGGL(scan_train_dg_reduce_kernel, dim3((unsigned)ceil_div(R * R, 256), (unsigned)Bi), dim3(256),",
+            "const dim3 gb((unsigned)ceil_div(D, 256), (unsigned)Bi);",
+            "hipLaunchKernelGGL(enorm_bwd_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)n_tok), dim3(256),",
+            # the arithmetic the mirror copies
+            "q = fmaxf(q, 0.f);", "sm.s[w] = sm.num[w] / fmaxf(g.enorm[off + w] * sqrtf(q), 1e-8f);",
+            "const float rn = (l2 || l1) ? 1.f / (st + 1e-8f) : (g.norm == 2 ? 1.f / st : 1.f);",
+        ),
+        "scan_train_i2t.hip": (
+            "constexpr int SI_RMAX = %d;" % S.SI_RMAX, "constexpr int SI_MAXW = %d;" % S.SI_MAXW,
+            "ITR_UNSUPPORTED(R < 1 || R > SI_RMAX,", "ITR_UNSUPPORTED(max_len > SI_MAXW,",
+            "if (R == SC_R) return launch_i2t<SC_R>(scan_train_i2t_fwd_kernel<SC_R, true>,",
+            "if (R < SC_R) return launch_i2t<SC_R>(scan_train_i2t_bwd_kernel<SC_R, false>,",
+            "return launch_i2t<SI_RMAX>(scan_train_i2t_bwd_kernel<SI_RMAX, false>,",
+            # caption_gram_kernel's slices, the row kernels' geometry
+            "__shared__ float xs[SI_MAXW][%d];" % (S.CGRAM_SLICE + 1), "for (int k0 = 0; k0 < D; k0 += %d) {" % S.CGRAM_SLICE,
+            "constexpr int NP = (SI_MAXW * SI_MAXW + 255) / 256;",
+            "hipLaunchKernelGGL(rownorm_i2t_kernel, dim3((unsigned)ceil_div(Bi * R, 4)), dim3(256),",
+            "for (int d = threadIdx.x; d < D; d += 256) {",
+            "hipLaunchKernelGGL(rowscale_add_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)(Bi * R)), dim3(256),",
+            "sm.s[r] = num / fmaxf(g.vnorm[i * R + r] * sqrtf(q), 1e-8f);",
+        ),
+        "autograd.py": ("ntp = (n_tok + %d) // %d * %d" % (S.NTP_ROUND - 1, S.NTP_ROUND, S.NTP_ROUND),),
+        "ops.py": ("return t.contiguous()",),
+    }
+    for name, lines in pins.items():
+        for line in lines:
+            assert line in text[name], "%s no longer says: %s" % (name, line)
+    assert text["autograd.py"].count(pins["autograd.py"][0]) == 2             # _ScanT2I.forward and _ScanI2T.forward
+    assert text["scan_train.hip"].count("for (int d = lane; d < D; d += 64)") == 2 and "for (int d = lane; d < D; d += 64)" in text["scan_train_i2t.hip"]
