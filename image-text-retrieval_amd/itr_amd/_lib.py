@@ -76,6 +76,8 @@ SIGNATURES = {
     "itr_mvm_scores": (i32, [vp, vp, vp, i64, i64, i32, i32, i64, vp]),
     "itr_hinge_maxviol_fwd": (i32, [vp, i32, i64, f32, i32, vp, vp, vp, vp, vp]),
     "itr_hinge_maxviol_bwd": (i32, [vp, i32, i64, f32, i32, vp, vp, vp, vp, i64, vp]),
+    "itr_hinge_groups_fwd": (i32, [vp, vp, i32, i64, f32, i32, vp, vp, vp, vp, vp]),
+    "itr_hinge_groups_bwd": (i32, [vp, vp, i32, i64, f32, i32, vp, vp, vp, vp, i64, vp]),
     "itr_scan_plan_tiles": (i32, [vp, i64, i32, vp, vp, vp]),
     "itr_sgr_plan_node_groups": (i32, [vp, i64, i32, vp, vp, vp]),
     "itr_scan_workspace_bytes": (sz, [i64, i32, i64, i64, i64, i32]),

@@ -29,7 +29,10 @@ DEFAULTS = dict(
     smry_lamda=0.01, lr_decay_gamma=0.1, drop=0.0,
     # not a key of the reference: True keeps the training split in device memory and collates every batch there
     # (datamodule/resident.py); False is the reference's DataLoader path
-    resident_data=False)
+    resident_data=False,
+    # not a key of the reference: True keeps two captions of the same image in a batch from being mined as each other's
+    # negatives (ops.hinge_loss(groups=ids // im_div)); False is the reference's loss, which masks the diagonal only
+    mask_same_image=False)
 
 NAMED = {
     'VSE_PP': dict(name="VSE++", data_name="f30k_precomp", vocab_type='pkl', val_step=10, img_dim=4096,

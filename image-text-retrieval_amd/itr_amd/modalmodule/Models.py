@@ -37,6 +37,7 @@ class base_module(nn.Module):
         self.optimizer = None
         self.params = None
         self.logger = None
+        self.train_im_div = None         # captions per image of the training set (train.py sets it); read by mask_same_image only
 
     def calculate_params(self):
         self.params_num = sum(p.numel() for p in self.params)
@@ -112,6 +113,28 @@ class base_module(nn.Module):
         captions = captions[idx.to(captions.device)][:, :max(lens)]
         return images, captions, lens, rows, toks, lens_all
 
+    def _hinge(self, scores, groups):
+        """The retrieval hinge of a training step; `groups` from _hinge_groups (None: exactly the reference's call)."""
+        if groups is None:
+            return ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'])
+        return ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'], groups=groups)
+
+    def _hinge_groups(self, ids, comm):
+        """config['mask_same_image'] off (the default, and every configuration read from an old checkpoint): None.  On: the image of
+        every pair, ids // train_im_div (host array), in the ROW ORDER OF THE SCORE MATRIX the step hands to the hinge -- the batch
+        order in one process, and the rank-major strided order of _dp_shard (rows q, q + world, ... of rank 0, then rank 1, ...) under
+        data parallelism, for every family: each shards by rank::world and gathers rank-major (SAEM's `order`, CAMERA's and VSRN's
+        `sel`).  Every rank derives it from the global batch without communication, like lens_all."""
+        if not self.config.get('mask_same_image', False):
+            return None
+        if not self.train_im_div:
+            raise ValueError("mask_same_image=True needs model.train_im_div, the captions per image of the training set "
+                             "(train.py sets it from the dataset's im_div; 5 for the precomp splits)")
+        ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
+        if comm.on:
+            ids = np.concatenate([ids[q::comm.world] for q in range(comm.world)])
+        return ids // int(self.train_im_div)
+
     # ---- shared by the GRU-family training steps
     def _train_towers(self, images, captions, lengths, pooled_images, last_state):
         """Differentiable towers on one batch -> (img_emb, packed word / caption embeddings, tok_off, lens).
@@ -169,7 +192,7 @@ class VSE_PP(base_module):
 
     def train_emb(self, train_data, *args, **kwargs):
         """One training step (Models.py:115-145)."""
-        images, _, _, captions, lengths, _, _, _ = train_data
+        images, _, _, captions, lengths, ids, _, _ = train_data
         if self.config['measure'] not in ('cosine', 'order'):
             raise ValueError("unknown measure:", self.config['measure'])
         pair_scores = ag.order_scores if self.config['measure'] == 'order' else ag.cosine_scores
@@ -178,6 +201,7 @@ class VSE_PP(base_module):
         self._log('lr', self.optimizer.param_groups[0]['lr'])
         self.optimizer.zero_grad()
         comm = self._dp_comm()
+        groups = self._hinge_groups(ids, comm)
         if comm.on:
             images, captions, lengths, rows, _, _ = self._dp_shard(comm, images, captions, lengths)
         with torch.enable_grad():
@@ -187,7 +211,7 @@ class VSE_PP(base_module):
                 scores = ag.dp_gather_rows(pair_scores(img, cap), comm, rows, reduce=False)
             else:
                 scores = pair_scores(img, cap)
-            loss = ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'])
+            loss = self._hinge(scores, groups)
             self._step(loss, scores.size(0))
 
     def forward_loss(self, img_emb, cap_emb):
@@ -223,7 +247,7 @@ class SCAN(base_module):
 
     def train_emb(self, train_data, *args, **kwargs):
         """One training step (Models.py:198-225)."""
-        images, _, _, captions, lengths, _, _, _ = train_data
+        images, _, _, captions, lengths, ids, _, _ = train_data
         cfg = self.config
         if cfg['cross_attn'] not in ('t2i', 'i2t'):
             raise ValueError("unknown first norm type:", cfg['raw_feature_norm'])
@@ -232,6 +256,7 @@ class SCAN(base_module):
         self._log('lr', self.optimizer.param_groups[0]['lr'])
         self.optimizer.zero_grad()
         comm = self._dp_comm()
+        groups = self._hinge_groups(ids, comm)
         if comm.on:
             images, captions, lengths, rows, toks, lens_all = self._dp_shard(comm, images, captions, lengths)
         with torch.enable_grad():
@@ -244,7 +269,7 @@ class SCAN(base_module):
             scores = score_fn(img, words, off, lens, cfg['raw_feature_norm'], cfg['agg_func'], cfg['lambda_lse'], cfg['lambda_softmax'])
             if comm.on:
                 scores = ag.dp_gather_rows(scores, comm, rows, reduce=False)
-            loss = ops.hinge_loss(scores, cfg['margin'], cfg['max_violation'])
+            loss = self._hinge(scores, groups)
             self._step(loss, scores.size(0))
 
     def forward_loss(self, img_emb, cap_emb, cap_lens):
@@ -314,7 +339,7 @@ class VSRN(base_module):
     def train_emb(self, train_data, *args, **kwargs):
         """One training step (Models.py:343-365): towers on the autograd tape -> retrieval hinge + captioning loss
         (calcualte_caption_loss :303-313) -> backward, clip_grad_norm_, Adam."""
-        images, _, _, captions, lengths, _, captions_mask, _ = train_data
+        images, _, _, captions, lengths, ids, captions_mask, _ = train_data
         if not isinstance(self.img_enc, ImgEncoder.EncoderImagePrecompAttn):
             raise NotImplementedError("VSRN.train_emb with use_txt_emb=False")
         if self.config['measure'] not in ('cosine', 'order'):
@@ -326,6 +351,7 @@ class VSRN(base_module):
             self._seeds = ag.DropoutSeeds()
         self._seeds.new_step()
         comm = self._dp_comm()
+        groups = self._hinge_groups(ids, comm)
         n_batch = len(lengths)
         if comm.on:
             # data parallel: a strided shard through the towers (the BatchNorms of the GCN and of the image tower take their
@@ -354,7 +380,7 @@ class VSRN(base_module):
                 img = ag.dp_gather_rows(img, comm, rows, reduce=False)
                 cap = ag.dp_gather_rows(cap, comm, rows, reduce=False)
             scores = (ag.order_scores if self.config['measure'] == 'order' else ag.cosine_scores)(img, cap)
-            retrieval_loss = ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'])
+            retrieval_loss = self._hinge(scores, groups)
             caption_loss = self.caption_model.caption_loss_train(gcn_emb, captions, self._dev(captions_mask), self._seeds,
                                                                  self.caption_model.training, batch_total=n_batch)
             caption_total = caption_loss.detach()
@@ -401,7 +427,7 @@ class SGRAF(base_module):
         self-attention dropout live, BatchNorm batch statistics), hinge on the B x B similarity matrix, backward,
         clip_grad_norm_, Adam.  The similarity module follows the reference's per-caption structure in training mode
         (Fusionmodule.encoder_similarity_train); evaluation uses the fused kernels."""
-        images, _, _, captions, lengths, _, _, _ = train_data
+        images, _, _, captions, lengths, ids, _, _ = train_data
         self.Eiters += 1
         self._log('Eit', self.Eiters)
         self._log('lr', self.optimizer.param_groups[0]['lr'])
@@ -410,6 +436,7 @@ class SGRAF(base_module):
         self._seeds.new_step()
         self.optimizer.zero_grad()
         comm = self._dp_comm()
+        groups = self._hinge_groups(ids, comm)
         shared = None
         if comm.on:
             # data parallel by CAPTION (the similarity module works caption by caption, each against all images): towers on a
@@ -430,7 +457,7 @@ class SGRAF(base_module):
                                                          self.sim_enc.training, seeds_global=shared)
             if comm.on:
                 sims = ag.dp_gather_rows(sims.t().contiguous(), comm, rows, reduce=False).t()      # (images, captions), both rank-major
-            loss = ops.hinge_loss(sims, self.config['margin'], self.config['max_violation'])
+            loss = self._hinge(sims, groups)
             self._step(loss, sims.size(0))
 
 
@@ -476,7 +503,9 @@ class SAEM(base_module):
     def train_emb(self, train_data, epoch=0):
         """One training step (Models.py:444-464): towers on the autograd tape (frozen BERT forward in training mode, head
         and image transformer layer differentiable), loss1 + alpha(epoch) * AngularLoss + 0.01 * sum ||W||, backward,
-        clip_grad_norm_, Adam.  utils.train_step never passes the epoch, so alpha is 0.5 there, as in the reference."""
+        clip_grad_norm_, Adam.  utils.train_step never passes the epoch, so alpha is 0.5 there, as in the reference.
+        mask_same_image masks the retrieval hinge (loss1) only: the angular term also takes the other rows of the batch as
+        negatives, and its kernel (csrc/aux_loss.hip) has no mask -- it is left as the reference computes it."""
         images, _, _, captions, lengths, ids, captions_mask, captions_type_ids = train_data
         self.Eiters += 1
         self._log('Eit', self.Eiters)
@@ -485,6 +514,7 @@ class SAEM(base_module):
             self._seeds = ag.DropoutSeeds()
         self._seeds.new_step()
         comm = self._dp_comm()
+        groups = self._hinge_groups(ids, comm)          # (in the gathered order: the same permutation as ids_all below)
         rows = None
         if comm.on:
             # data parallel: strided shard of the global batch through the towers, both embedding sets all-gathered; every
@@ -511,7 +541,7 @@ class SAEM(base_module):
                 lengths, ids = lengths_all, ids_all
             # criterion = hinge on pdist_cos (Objectives.py:310-323: rows renormalised, no eps), on the tape
             scores = ag.cosine_scores(ag.l2norm_rows(img, eps=0.0), ag.l2norm_rows(cap, eps=0.0))
-            loss1 = ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'])
+            loss1 = self._hinge(scores, groups)
             alpha = 0 if epoch > 20 else 0.5 * (0.1 ** (epoch // 5))
             loss2 = self.criterion_2(img, cap, lengths, ids)
             l2_reg = torch.zeros((), device=img.device)
@@ -568,7 +598,7 @@ class CAMERA(base_module):
         """One training step (Models.py:613-645): towers on the autograd tape (frozen BERT forward in training mode, AGSA with
         BatchNorm batch statistics, dilated-convolution summarisation), multi-view matching, bidirectional hinge + smry_lamda *
         diversity regulariser, backward, clip_grad_norm_, Adam."""
-        images, boxes, imgs_wh, captions, _, _, captions_mask, captions_type_ids = train_data
+        images, boxes, imgs_wh, captions, _, ids, captions_mask, captions_type_ids = train_data
         self.Eiters += 1
         self._log('Eit', self.Eiters)
         self._log('lr', self.optimizer.param_groups[0]['lr'])
@@ -576,6 +606,7 @@ class CAMERA(base_module):
             self._seeds = ag.DropoutSeeds()
         self._seeds.new_step()
         comm = self._dp_comm()
+        groups = self._hinge_groups(ids, comm)
         if comm.on:
             # data parallel (like SAEM): a strided shard of the global batch through the towers -- every BatchNorm inside takes
             # its statistics over the rows of ALL ranks (ag.bn_sync: one small all-reduce each way) -- then the multi-view
@@ -598,7 +629,7 @@ class CAMERA(base_module):
                 cap = ag.dp_gather_rows(cap, comm, rows, reduce=False)
                 smry_mat = ag.dp_gather_rows(smry_mat, comm, rows, reduce=False)
             sim_mat = ag.mvm_scores(img, cap)
-            ranking_loss = ops.hinge_loss(sim_mat, self.config['margin'], self.config['max_violation'])
+            ranking_loss = self._hinge(sim_mat, groups)
             div_reg = self.crit_div(smry_mat)
             loss = ranking_loss + div_reg * self.config['smry_lamda']
             self._log('Rank_Loss', ranking_loss.detach(), len(sim_mat))

@@ -98,12 +98,16 @@ class ContrastiveLoss(nn.Module):
             raise NotImplementedError("SAEM's loss terms are composed in SAEM.forward_loss / train_emb")
         return ag.order_scores(im, s) if self.sim is order_sim else ag.cosine_scores(im, s)
 
-    def forward(self, im, s=None, s_l=None):
+    def forward(self, im, s=None, s_l=None, groups=None):
+        """`groups` (one integer per pair, e.g. the image id): pairs of one group are no negatives of each other (ops.hinge_loss);
+        None is the reference's loss."""
         if torch.is_grad_enabled() and (im.requires_grad or (torch.is_tensor(s) and s.requires_grad)):
             scores = self._sim_on_tape(im, s, s_l)
         else:
             scores = self.sim(im, s, s_l, self.config)
-        return ops.hinge_loss(scores, self.margin, self.max_violation)
+        if groups is None:
+            return ops.hinge_loss(scores, self.margin, self.max_violation)
+        return ops.hinge_loss(scores, self.margin, self.max_violation, groups=groups)
 
 
 class TripletLoss(nn.Module):
@@ -114,8 +118,10 @@ class TripletLoss(nn.Module):
         self.margin = margin
         self.max_violation = max_violation
 
-    def forward(self, scores):
-        return ops.hinge_loss(scores, self.margin, self.max_violation)
+    def forward(self, scores, groups=None):
+        if groups is None:
+            return ops.hinge_loss(scores, self.margin, self.max_violation)
+        return ops.hinge_loss(scores, self.margin, self.max_violation, groups=groups)
 
 
 class DiversityRegularization(nn.Module):

@@ -320,30 +320,66 @@ def mvm_scores(imgs, caps, out=None):
 
 
 # ------------------------------------------------------------------------------------------
-def hinge_fwd(scores, margin, max_violation):
-    """-> (loss[1], row_arg, col_arg)."""
+def _hinge_groups(groups, B, device):
+    """`groups` of the masked hinge -> int32 device tensor [B].  Host input (list, numpy, CPU tensor) is checked on the host and
+    uploaded through pinned staging (one small copy); an integer device tensor is used where it lies (an int64 one is range-checked
+    there, which reads one flag back)."""
+    if torch.is_tensor(groups) and groups.is_cuda:
+        if groups.dtype.is_floating_point or groups.dtype == torch.bool or groups.dtype.is_complex:
+            raise TypeError("hinge loss: groups must be integers, got %s" % groups.dtype)
+        if groups.dim() != 1 or groups.shape[0] != B:
+            raise ValueError("hinge loss: groups must have length %d, got shape %s" % (B, tuple(groups.shape)))
+        if groups.dtype != torch.int32:
+            if groups.dtype.itemsize > 2 and bool(((groups < -2 ** 31) | (groups > 2 ** 31 - 1)).any()):
+                raise ValueError("hinge loss: a group value does not fit int32")
+            groups = groups.to(torch.int32)
+        return groups.contiguous()
+    arr = np.asarray(groups.numpy() if torch.is_tensor(groups) else groups)
+    if arr.dtype.kind not in 'iu':
+        raise TypeError("hinge loss: groups must be integers, got %s" % arr.dtype)
+    if arr.ndim != 1 or arr.shape[0] != B:
+        raise ValueError("hinge loss: groups must have length %d, got shape %s" % (B, arr.shape))
+    if arr.size and (int(arr.min()) < -2 ** 31 or int(arr.max()) > 2 ** 31 - 1):
+        raise ValueError("hinge loss: a group value does not fit int32")
+    return h2d(arr.astype(np.int32), device)
+
+
+def hinge_fwd(scores, margin, max_violation, groups=None):
+    """-> (loss[1], row_arg, col_arg).  `groups` (length B, integers): entries (i, j), i != j, of one group are no negatives
+    (itr_hinge_groups_fwd); None is the reference's loss, which masks the diagonal only."""
     lib = _lib.load()
     scores = _dev(scores, name="scores")
     if scores.dim() != 2 or scores.shape[0] != scores.shape[1]:
         raise ValueError("hinge loss needs a square score matrix, got %s" % (tuple(scores.shape),))
     B = scores.shape[0]
+    if groups is not None:
+        groups = _hinge_groups(groups, B, scores.device)
     loss = torch.empty(1, device=scores.device, dtype=torch.float32)
     row_arg = torch.empty(B, device=scores.device, dtype=torch.int32)
     col_arg = torch.empty(B, device=scores.device, dtype=torch.int32)
     ws = torch.empty(2 * B, device=scores.device, dtype=torch.float32)
-    _lib.check(lib.itr_hinge_maxviol_fwd(_p(scores), B, B, float(margin), int(bool(max_violation)), _p(loss),
-                                         _p(row_arg), _p(col_arg), _p(ws), _stream()))
+    if groups is None:
+        _lib.check(lib.itr_hinge_maxviol_fwd(_p(scores), B, B, float(margin), int(bool(max_violation)), _p(loss),
+                                             _p(row_arg), _p(col_arg), _p(ws), _stream()))
+    else:
+        _lib.check(lib.itr_hinge_groups_fwd(_p(scores), _p(groups), B, B, float(margin), int(bool(max_violation)), _p(loss),
+                                            _p(row_arg), _p(col_arg), _p(ws), _stream()))
     return loss, row_arg, col_arg
 
 
-def hinge_bwd(scores, margin, max_violation, row_arg, col_arg, grad_loss):
+def hinge_bwd(scores, margin, max_violation, row_arg, col_arg, grad_loss, groups=None):
     lib = _lib.load()
     scores = _dev(scores, name="scores")
     B = scores.shape[0]
     g = _dev(grad_loss.reshape(1), name="grad_loss")
     dS = torch.empty_like(scores)
-    _lib.check(lib.itr_hinge_maxviol_bwd(_p(scores), B, B, float(margin), int(bool(max_violation)), _p(row_arg),
-                                         _p(col_arg), _p(g), _p(dS), B, _stream()))
+    if groups is None:
+        _lib.check(lib.itr_hinge_maxviol_bwd(_p(scores), B, B, float(margin), int(bool(max_violation)), _p(row_arg),
+                                             _p(col_arg), _p(g), _p(dS), B, _stream()))
+    else:
+        groups = _hinge_groups(groups, B, scores.device)
+        _lib.check(lib.itr_hinge_groups_bwd(_p(scores), _p(groups), B, B, float(margin), int(bool(max_violation)), _p(row_arg),
+                                            _p(col_arg), _p(g), _p(dS), B, _stream()))
     return dS
 
 
@@ -362,9 +398,29 @@ class _HingeFn(torch.autograd.Function):
         return hinge_bwd(scores, ctx.margin, ctx.mv, ra, ca, grad.contiguous()), None, None
 
 
-def hinge_loss(scores, margin=0.2, max_violation=False):
-    """Differentiable (w.r.t. scores) bidirectional hinge loss, HIP forward and backward."""
-    return _HingeFn.apply(scores, margin, max_violation)
+class _HingeGroupsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, margin, max_violation, groups):
+        scores = scores.contiguous()
+        loss, ra, ca = hinge_fwd(scores, margin, max_violation, groups)
+        ctx.save_for_backward(scores, ra, ca, groups)
+        ctx.margin, ctx.mv = margin, max_violation
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad):
+        scores, ra, ca, groups = ctx.saved_tensors
+        return hinge_bwd(scores, ctx.margin, ctx.mv, ra, ca, grad.contiguous(), groups), None, None, None
+
+
+def hinge_loss(scores, margin=0.2, max_violation=False, groups=None):
+    """Differentiable (w.r.t. scores) bidirectional hinge loss, HIP forward and backward.  `groups` (length-B integer tensor, numpy
+    array or list; no gradient): pairs of one group -- captions of the same image -- are not mined as negatives of each other."""
+    if groups is None:
+        return _HingeFn.apply(scores, margin, max_violation)
+    if scores.dim() != 2 or scores.shape[0] != scores.shape[1]:
+        raise ValueError("hinge loss needs a square score matrix, got %s" % (tuple(scores.shape),))
+    return _HingeGroupsFn.apply(scores, margin, max_violation, _hinge_groups(groups, scores.shape[0], scores.device))
 
 
 # ------------------------------------------------------------------------------------------

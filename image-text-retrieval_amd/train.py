@@ -34,6 +34,10 @@ def train(_config):
     else:
         start_epoch, best_rsum, best_r1 = 0, 0, 0
         model = models.get_model(_config).cuda()
+    # captions per image of the training set, for mask_same_image (ids // im_div names a caption's image): the resident set's
+    # own figure on that path, the PrecompDataset's on the DataLoader path
+    resident_set = getattr(train_loader, 'resident_set', None)
+    model.train_im_div = int(resident_set.im_div if resident_set is not None else train_loader.dataset.im_div)
     for epoch in range(start_epoch, _config['num_epochs']):
         utils.adjust_learning_rate(_config, model.optimizer, epoch)
         best_rsum, best_r1 = utils.train_step(_config, train_loader, model, epoch, val_loader, best_rsum, best_r1)

@@ -183,6 +183,22 @@ int itr_hinge_maxviol_fwd(const float *S, int B, int64_t ldS, float margin, int 
 int itr_hinge_maxviol_bwd(const float *S, int B, int64_t ldS, float margin, int max_violation,
                           const int32_t *row_arg, const int32_t *col_arg, const float *grad_loss,
                           float *dS, int64_t lddS, itr_stream_t stream);
+/* The same loss (Objectives.py:93-115, :492-517) when several rows of a batch share their positive: group[B] (int32, device) names
+ * the image of every pair, and an entry (i, j) with i != j and group[i] == group[j] is MASKED -- it is no negative:
+ *   loss = sum_i red_{j != i, j unmasked}[m + S_ij - S_ii]_+ + sum_j red_{i != j, i unmasked}[m + S_ij - S_jj]_+.
+ * A masked entry costs 0 like the diagonal, is never a row or column arg-max, gets dS = 0 and adds nothing to the diagonal's
+ * gradient; the positive stays the diagonal.  The mask is symmetric, so one vector serves rows and columns; any int32 value is a
+ * group.  Ties as above: the larger cost wins, on equal costs the lower index, chosen among the UNMASKED candidates (and the
+ * diagonal, whose cost is 0).  The forward never writes a masked index into row_arg / col_arg, and the backward checks the mask
+ * again.  With all groups distinct every output has the bits of the pair above.  Launches, determinism (no float atomics) and the
+ * host checks are the pair's: null S / group / loss / cost_ws / dS / grad_loss, B < 1, ldS < B, lddS < B, missing args with
+ * max_violation -> ITR_ERR_BADARG.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+int itr_hinge_groups_fwd(const float *S, const int32_t *group, int B, int64_t ldS, float margin, int max_violation,
+                         float *loss, int32_t *row_arg, int32_t *col_arg, float *cost_ws /* [2B] */, itr_stream_t stream);
+int itr_hinge_groups_bwd(const float *S, const int32_t *group, int B, int64_t ldS, float margin, int max_violation,
+                         const int32_t *row_arg, const int32_t *col_arg, const float *grad_loss,
+                         float *dS, int64_t lddS, itr_stream_t stream);
 
 /* ---- a6: xattn_score_t2i / xattn_score_i2t (Objectives.py:329-476) ---------------------
  * img [Ni,R,D]; words [n_rows,D] with caption c owning rows cap_off[c] .. cap_off[c]+len[c]-1

@@ -115,13 +115,13 @@ def oracle_cpu_step(model_name, batch, cfg, model=None):
     return time.perf_counter() - t0
 
 
-def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=None):
+def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=None, mask_same_image=False):
     from itr_amd import config as C
     from itr_amd.modalmodule import get_model
     from itr_amd.metricmodule.evaluation import LogCollector
     dev = dev or torch.device("cuda", 0)
-    cfg = C.build_config(['with', model_name, 'data_name=coco_precomp', 'bi_gru=True', 'max_violation=True'] +
-                         (['module_name=' + module] if model_name == 'SGRAF' else []))
+    cfg = C.build_config(['with', model_name, 'data_name=coco_precomp', 'bi_gru=True', 'max_violation=True',
+                          'mask_same_image=%s' % bool(mask_same_image)] + (['module_name=' + module] if model_name == 'SGRAF' else []))
     cfg['vocab_size'] = V_COCO
     cfg['img_dim'] = 2048        # precomp region features
     if model_name in ('SAEM', 'CAMERA'):
@@ -130,6 +130,7 @@ def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=N
         cfg.update(bert_config_file=cfg_file, init_checkpoint=ckpt, trans_cfg=trans, vocab_size=30522, batch_size=batch)
     torch.manual_seed(0)
     model = get_model(cfg)
+    model.train_im_div = 5           # the precomp splits' captions per image; the batches' ids are 0 .. B-1, so the mask has groups of 5
     model.train_start()
     model.logger = LogCollector()
     rng = np.random.RandomState(0)
@@ -216,6 +217,7 @@ def main():
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--cpu", action="store_true", help="time the oracle's training step on the host cores beside VSE++ / SCAN")
     ap.add_argument("--budget", type=float, default=1e9, help="--all: seconds after which no further family is started")
+    ap.add_argument("--mask-same-image", action="store_true", help="time the step with mask_same_image=True (the hinge with the group mask)")
     a = ap.parse_args()
     t_start = time.perf_counter()
     rows = {}
@@ -226,7 +228,7 @@ def main():
             rows[name] = {"error": "not started: the time budget of the run was spent"}
             continue
         try:
-            r = run(model_name, module, a.batch or batch, a.steps, a.warmup, cpu=a.cpu)
+            r = run(model_name, module, a.batch or batch, a.steps, a.warmup, cpu=a.cpu, mask_same_image=a.mask_same_image)
         except Exception as e:      # noqa: BLE001  (one family must not take the others' rows with it)
             r = {"family": name, "error": "%s: %s" % (type(e).__name__, e)}
         rows[name] = r
