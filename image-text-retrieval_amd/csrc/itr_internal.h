@@ -55,6 +55,10 @@ int gemm_tn(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, 
 int norm_rows(const float *x, float *y, int64_t rows, int dim, float eps, int kind, int take_abs, hipStream_t st);
 // ---- scan_train.hip: once per (kernel, device), under a mutex
 int allow_dynamic_lds(const void *kernel, size_t bytes);
+// row L2 norms (no eps) and their backward dX[row] += dn[row] X[row] / ||X[row]||: the words in t2i, the regions in i2t (scan_train_i2t.hip)
+__global__ void rownorm_train_kernel(const float *__restrict__ x, int64_t rows, int D, float *__restrict__ out);
+__global__ void rownorm_bwd_kernel(const float *__restrict__ X, const float *__restrict__ xnorm, const float *__restrict__ dn, int64_t rows, int D,
+                                   float *__restrict__ dX);
 // ---- scan_xattn.hip
 struct ScanTileMeta;
 // the SCAN workspace: tile records and tile-packed words, then the t2i (mode 0) or the i2t (mode 1) buffers in the same space

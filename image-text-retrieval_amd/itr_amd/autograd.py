@@ -375,26 +375,51 @@ def order_scores(im, s):
     return _Order.apply(im, s)
 
 
+def _scan_pair_dots(who, V, E, cap_len):
+    """What both directions of SCAN training start with: the word axis zero-padded to a multiple of 32 (ntp) so that every GEMM whose
+    contraction runs over the words (dV = dA E) takes the branch-free kernel; padded columns of A / dA are zero and never read by
+    the pair kernels.  -> V2 [Bi*R, D], Ep [ntp, D], A = V2 Ep^T, (Bi, Bc, n_tok, ntp, R, D)."""
+    V = _dev(V, name="images")
+    E = _dev(E, name="words")
+    Bi, R, D = V.shape
+    if E.dim() != 2 or E.shape[1] != D:
+        raise ValueError("%s: images (.., %d) vs words %s" % (who, D, tuple(E.shape)))
+    n_tok = E.shape[0]
+    ntp = (n_tok + 31) // 32 * 32
+    V2 = V.reshape(Bi * R, D)
+    Ep = torch.zeros(ntp, D, device=V.device, dtype=torch.float32)
+    Ep[:n_tok] = E
+    A = _gemm_nt(V2, Ep)                                              # raw dot products of all pairs, [Bi*36, ntp]
+    return V2, Ep, A, (Bi, cap_len.numel(), n_tok, ntp, R, D)
+
+
+def _scan_pair_grads(dA, V2, Ep):
+    """The D-long contractions of both backwards: dV = dA E, dE = dA^T V (the Gram and norm terms are added by the finish entry)."""
+    dV = _gemm_nt(dA, transpose2d(Ep))                                # dA [Bi*36, ntp] . E [ntp, D]
+    dE = _gemm_tn(dA, V2)                                             # dA^T [ntp, Bi*36] . V [Bi*36, D]
+    return dV, dE
+
+
+def _scan_train_args(images, cap_off, cap_lens, raw_feature_norm, agg_func):
+    """Checked options of scan_t2i_scores / scan_i2t_scores -> host lengths, cap_off and lengths on the device, norm and agg codes."""
+    if raw_feature_norm not in _NORMS:
+        raise ValueError("unknown first norm type:", raw_feature_norm)
+    if agg_func not in _AGGS:
+        raise ValueError("unknown aggfunc: {}".format(agg_func))
+    lens = _host_i32(cap_lens)
+    dev = images.device
+    off = cap_off if torch.is_tensor(cap_off) else h2d(np.asarray(cap_off, np.int64), dev)
+    return lens, _dev(off, torch.int64, "cap_off"), h2d(lens.copy(), dev), _NORMS[raw_feature_norm], _AGGS[agg_func]
+
+
 class _ScanT2I(torch.autograd.Function):
-    """The word axis is zero-padded to a multiple of 32 (ntp) so that every GEMM whose contraction runs over the words
-    (dV = dA E) takes the branch-free kernel; padded columns of A / dA are zero and never read by the pair kernels."""
+    """xattn_score_t2i on a training batch (scan_train.hip)."""
 
     @staticmethod
     def forward(ctx, V, E, cap_off, cap_len, max_len, norm, agg, ls, ll):
         lib = _lib.load()
-        V = _dev(V, name="images")
-        E = _dev(E, name="words")
-        Bi, R, D = V.shape
-        if E.dim() != 2 or E.shape[1] != D:
-            raise ValueError("scan_t2i_scores: images (.., %d) vs words %s" % (D, tuple(E.shape)))
-        n_tok = E.shape[0]
-        ntp = (n_tok + 31) // 32 * 32
-        Bc = cap_len.numel()
-        dev = V.device
-        V2 = V.reshape(Bi * R, D)
-        Ep = torch.zeros(ntp, D, device=dev, dtype=torch.float32)
-        Ep[:n_tok] = E
-        A = _gemm_nt(V2, Ep)                                          # raw dot products of all pairs, [Bi*36, ntp]
+        V2, Ep, A, (Bi, Bc, n_tok, ntp, R, D) = _scan_pair_dots("scan_t2i_scores", V, E, cap_len)
+        dev = V2.device
         G = _f32(Bi, R, R, dev=dev)
         enorm = _f32(ntp, dev=dev)
         _lib.check(lib.itr_scan_train_prepare(_p(V2), _p(Ep), Bi, ntp, R, D, _p(G), _p(enorm), _stream()))
@@ -417,8 +442,7 @@ class _ScanT2I(torch.autograd.Function):
         denp = torch.zeros(Bi, ntp, device=dev, dtype=torch.float32)
         _lib.check(lib.itr_scan_train_bwd(_p(A), ntp, _p(G), _p(enorm), _p(cap_off), _p(cap_len), Bi, Bc, ntp, R, D, max_len, norm,
                                           agg, ls, ll, _p(dS), _p(dA), _p(dGp), _p(denp), _stream()))
-        dV = _gemm_nt(dA, transpose2d(Ep))                            # dA [Bi*36, ntp] . E [ntp, D]
-        dE = _gemm_tn(dA, V2)                                         # dA^T [ntp, Bi*36] . V [Bi*36, D]
+        dV, dE = _scan_pair_grads(dA, V2, Ep)
         den = colsum(denp)
         _lib.check(lib.itr_scan_train_finish(_p(dGp), Bi, Bc, _p(V2), _p(Ep), _p(enorm), _p(den), ntp, R, D, _p(dV), _p(dE), _stream()))
         return dV.reshape(Bi, R, D), dE[:n_tok], None, None, None, None, None, None, None
@@ -427,15 +451,8 @@ class _ScanT2I(torch.autograd.Function):
 def scan_t2i_scores(images, words_packed, cap_off, cap_lens, raw_feature_norm='clipped_l2norm', agg_func='LogSumExp',
                     lambda_lse=6.0, lambda_softmax=9.0):
     """xattn_score_t2i on a training batch -> (n_img, n_cap), differentiable w.r.t. images and words."""
-    if raw_feature_norm not in _NORMS:
-        raise ValueError("unknown first norm type:", raw_feature_norm)
-    if agg_func not in _AGGS:
-        raise ValueError("unknown aggfunc: {}".format(agg_func))
-    lens = _host_i32(cap_lens)
-    dev = images.device
-    off = cap_off if torch.is_tensor(cap_off) else h2d(np.asarray(cap_off, np.int64), dev)
-    return _ScanT2I.apply(images, words_packed, _dev(off, torch.int64, "cap_off"), h2d(lens.copy(), dev), int(lens.max()),
-                          _NORMS[raw_feature_norm], _AGGS[agg_func], float(lambda_softmax), float(lambda_lse))
+    lens, off, lens_dev, norm, agg = _scan_train_args(images, cap_off, cap_lens, raw_feature_norm, agg_func)
+    return _ScanT2I.apply(images, words_packed, off, lens_dev, int(lens.max()), norm, agg, float(lambda_softmax), float(lambda_lse))
 
 
 class _ScanI2T(torch.autograd.Function):
@@ -444,19 +461,8 @@ class _ScanI2T(torch.autograd.Function):
     @staticmethod
     def forward(ctx, V, E, cap_off, cap_len, h_off, h_total, max_len, norm, agg, ls, ll):
         lib = _lib.load()
-        V = _dev(V, name="images")
-        E = _dev(E, name="words")
-        Bi, R, D = V.shape
-        if E.dim() != 2 or E.shape[1] != D:
-            raise ValueError("scan_i2t_scores: images (.., %d) vs words %s" % (D, tuple(E.shape)))
-        n_tok = E.shape[0]
-        ntp = (n_tok + 31) // 32 * 32
-        Bc = cap_len.numel()
-        dev = V.device
-        V2 = V.reshape(Bi * R, D)
-        Ep = torch.zeros(ntp, D, device=dev, dtype=torch.float32)
-        Ep[:n_tok] = E
-        A = _gemm_nt(V2, Ep)
+        V2, Ep, A, (Bi, Bc, n_tok, ntp, R, D) = _scan_pair_dots("scan_i2t_scores", V, E, cap_len)
+        dev = V2.device
         H = _f32(h_total, dev=dev)
         vnorm = _f32(Bi * R, dev=dev)
         _lib.check(lib.itr_scan_train_i2t_prepare(_p(V2), _p(Ep), _p(cap_off), _p(cap_len), _p(h_off), Bi, Bc, R, D, _p(H), _p(vnorm), _stream()))
@@ -479,8 +485,7 @@ class _ScanI2T(torch.autograd.Function):
         dvnp = _f32(Bc, Bi * R, dev=dev)
         _lib.check(lib.itr_scan_train_i2t_bwd(_p(A), ntp, _p(H), _p(h_off), h_total, _p(vnorm), _p(cap_off), _p(cap_len), Bi, Bc, ntp, R, D,
                                               max_len, norm, agg, ls, ll, _p(dS), _p(dA), _p(dHp), _p(dvnp), _stream()))
-        dV = _gemm_nt(dA, transpose2d(Ep))
-        dE = _gemm_tn(dA, V2)
+        dV, dE = _scan_pair_grads(dA, V2, Ep)
         dH = colsum(dHp)
         dvn = colsum(dvnp)
         _lib.check(lib.itr_scan_train_i2t_finish(_p(dH), _p(h_off), _p(cap_off), _p(cap_len), Bc, _p(Ep), _p(V2), _p(vnorm), _p(dvn), Bi, R, D,
@@ -491,17 +496,10 @@ class _ScanI2T(torch.autograd.Function):
 def scan_i2t_scores(images, words_packed, cap_off, cap_lens, raw_feature_norm='clipped_l2norm', agg_func='LogSumExp',
                     lambda_lse=6.0, lambda_softmax=9.0):
     """xattn_score_i2t on a training batch -> (n_img, n_cap), differentiable w.r.t. images and words."""
-    if raw_feature_norm not in _NORMS:
-        raise ValueError("unknown first norm type:", raw_feature_norm)
-    if agg_func not in _AGGS:
-        raise ValueError("unknown aggfunc: {}".format(agg_func))
-    lens = _host_i32(cap_lens)
-    dev = images.device
-    off = cap_off if torch.is_tensor(cap_off) else h2d(np.asarray(cap_off, np.int64), dev)
+    lens, off, lens_dev, norm, agg = _scan_train_args(images, cap_off, cap_lens, raw_feature_norm, agg_func)
     sq = lens.astype(np.int64) ** 2
     h_off = np.concatenate([[0], np.cumsum(sq)[:-1]]).astype(np.int64)
-    return _ScanI2T.apply(images, words_packed, _dev(off, torch.int64, "cap_off"), h2d(lens.copy(), dev),
-                          h2d(h_off, dev), int(sq.sum()), int(lens.max()), _NORMS[raw_feature_norm], _AGGS[agg_func],
+    return _ScanI2T.apply(images, words_packed, off, lens_dev, h2d(h_off, images.device), int(sq.sum()), int(lens.max()), norm, agg,
                           float(lambda_softmax), float(lambda_lse))
 
 

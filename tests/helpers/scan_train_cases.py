@@ -43,13 +43,12 @@ CAP_EXEMPT_D = 1              # see the module docstring
 FALLBACK_SHARE = 0.02
 
 # geometry of the kernels (pinned to csrc/ by tests/test_scan_train_case_table.py)
-ST_RMAX, ST_MAXW = 100, 96                  # scan_train.hip:26-27
-SI_RMAX, SI_MAXW = 100, 96                  # scan_train_i2t.hip:17-18
+ST_RMAX, ST_MAXW = 100, 96                  # scan_train_pair.h:26-27 (both directions)
 SC_R = 36                                   # scan_common.h:7
-GRAM_MFMA_RMAX = 48                         # scan_train.hip:409
-DG_UNROLL = 16                              # scan_train.hip:293
-CGRAM_SLICE = 32                            # scan_train_i2t.hip:299
-NTP_ROUND = 32                              # autograd.py: _ScanT2I.forward / _ScanI2T.forward
+GRAM_MFMA_RMAX = 48                         # scan_train.hip:224
+DG_UNROLL = 16                              # scan_train.hip:128
+CGRAM_SLICE = 32                            # scan_train_i2t.hip:124
+NTP_ROUND = 32                              # autograd.py: _scan_pair_dots (_ScanT2I.forward and _ScanI2T.forward)
 
 SEAMS = {}          # direction -> {parameter: values that must appear in the table}, filled next to the cases
 CASES = []
@@ -67,8 +66,8 @@ def ceil_div(a, b):
 # ---------------------------------------------------------------------------------------------------------------------
 # mirrors of the host-side routing
 def t2i_pair_route(R, max_len, backward):
-    """scan_train.hip:367-368 (check_train_args), :431-442 (itr_scan_train_fwd), :453-464 (itr_scan_train_bwd): the pair kernel's
-    instantiation (MAXW, RMAX, FIXED), or 'rejected'."""
+    """scan_train_pair.h:251-252 (check_train_args), scan_train.hip:246-257 (itr_scan_train_fwd), :268-279 (itr_scan_train_bwd): the
+    pair kernel's instantiation (MAXW, RMAX, FIXED), or 'rejected'."""
     if R < 1 or R > ST_RMAX or max_len > ST_MAXW:
         return 'rejected'
     if backward and R > SC_R and max_len > 64:
@@ -84,29 +83,29 @@ def t2i_pair_route(R, max_len, backward):
 
 
 def i2t_pair_route(R, max_len=1):
-    """scan_train_i2t.hip:329-330 (check_i2t), :373-375 (itr_scan_train_i2t_fwd), :389-391 (itr_scan_train_i2t_bwd): (RMAX, FIXED),
-    forward and backward alike, or 'rejected'."""
-    if R < 1 or R > SI_RMAX or max_len > SI_MAXW:
+    """scan_train_pair.h:251-252 (check_train_args), scan_train_i2t.hip:177-179 (itr_scan_train_i2t_fwd), :193-195
+    (itr_scan_train_i2t_bwd): (RMAX, FIXED), forward and backward alike, or 'rejected'."""
+    if R < 1 or R > ST_RMAX or max_len > ST_MAXW:
         return 'rejected'
     if R == SC_R:
         return (SC_R, True)
-    return (SC_R, False) if R < SC_R else (SI_RMAX, False)
+    return (SC_R, False) if R < SC_R else (ST_RMAX, False)
 
 
 def gram_route(R, D, aligned):
-    """scan_train.hip:409-415 (itr_scan_train_prepare): the kernel that computes G = V V^T."""
+    """scan_train.hip:224-230 (itr_scan_train_prepare): the kernel that computes G = V V^T."""
     if R <= GRAM_MFMA_RMAX and D % 4 == 0 and aligned:
         return 'mfma'
     return 'gram36' if R == SC_R else 'train_gram'
 
 
 def dg_reduce_blocks(R):
-    """scan_train.hip:475 (itr_scan_train_finish): workgroups per image of scan_train_dg_reduce_kernel."""
+    """scan_train.hip:290 (itr_scan_train_finish): workgroups per image of scan_train_dg_reduce_kernel."""
     return ceil_div(R * R, 256)
 
 
 def ntp(n_tok):
-    """autograd.py: _ScanT2I.forward / _ScanI2T.forward: the padded word count."""
+    """autograd.py: _scan_pair_dots (_ScanT2I.forward and _ScanI2T.forward): the padded word count."""
     return (n_tok + NTP_ROUND - 1) // NTP_ROUND * NTP_ROUND
 
 
@@ -128,7 +127,7 @@ def oracle(x, xa, lens, norm, agg):
 
 
 def _first_norm(a, norm, dim):
-    """scan_train.hip:81-101 / scan_train_i2t.hip:62-82: b = leaky(a) | a; u = b / (||b|| + eps) | b / (sum |b| + eps) | softmax(a) | b."""
+    """scan_train_pair.h:66-88 (pair_forward, both directions): b = leaky(a) | a; u = b / (||b|| + eps) | b / (sum |b| + eps) | softmax(a) | b."""
     b = torch.where(a > 0, a, 0.1 * a) if norm in ('clipped_l2norm', 'clipped', 'clipped_l1norm') else a
     if norm in ('clipped_l2norm', 'l2norm'):
         return b / ((b * b).sum(dim, keepdim=True).sqrt() + 1e-8)
@@ -141,7 +140,7 @@ def _first_norm(a, norm, dim):
 
 
 def _aggregate(s, agg):
-    """scan_train.hip:157-170 / scan_train_i2t.hip:130-143 (the LSE with its maximum taken out first)."""
+    """scan_train_pair.h:137-154 (pair_aggregate, both directions; the LSE with its maximum taken out first)."""
     if agg == 'LogSumExp':
         return torch.logsumexp(s * LAMBDA_LSE, 1) / LAMBDA_LSE
     if agg == 'Max':
@@ -150,14 +149,15 @@ def _aggregate(s, agg):
 
 
 def mirror_t2i(x, lens, norm, agg):
-    """scan_train.hip:5-13 (header) and :71-145 (pair_forward): A = V E^T for all pairs from one product, G_i = V_i V_i^T, ||e_w||;
-    per pair u = first norm over the caption's words per region, p = softmax_r(lambda_s u), num_w = sum_r p a, q_w = p^T G p
-    (clamped at 0, :140), s_w = num_w / max(||e_w|| sqrt(q_w), 1e-8) (:142)."""
+    """scan_train.hip:5-14 (header), :73-79 (t2i_pair_forward) and scan_train_pair.h:63-134 (pair_forward with context = regions,
+    query = words): A = V E^T for all pairs from one product, G_i = V_i V_i^T, ||e_w||; per pair u = first norm over the caption's
+    words per region, p = softmax_r(lambda_s u), num_w = sum_r p a, q_w = p^T G p (clamped at 0, scan_train_pair.h:129),
+    s_w = num_w / max(||e_w|| sqrt(q_w), 1e-8) (:131)."""
     V, E = x['images'], x['words']
     Bi, R, D = V.shape
-    A = (V.reshape(Bi * R, D) @ E.t()).view(Bi, R, -1)               # autograd.py: _ScanT2I.forward: A = _gemm_nt(V2, Ep)
-    G = V @ V.transpose(1, 2)                                          # scan_train.hip:409-415
-    enorm = (E * E).sum(1).sqrt()                                      # scan_train.hip:345-353
+    A = (V.reshape(Bi * R, D) @ E.t()).view(Bi, R, -1)               # autograd.py: _scan_pair_dots: A = _gemm_nt(V2, Ep)
+    G = V @ V.transpose(1, 2)                                          # scan_train.hip:224-230
+    enorm = (E * E).sum(1).sqrt()                                      # scan_train.hip:180-188 (rownorm_train_kernel)
     cols = []
     for o, W in zip(_offsets(lens), lens):
         a = A[:, :, o:o + W]
@@ -170,17 +170,18 @@ def mirror_t2i(x, lens, norm, agg):
 
 
 def mirror_i2t(x, lens, norm, agg):
-    """scan_train_i2t.hip:3-8 (header) and :52-118 (i2t_pair_forward): A = V E^T, H_c = E_c E_c^T, ||v_r||; per pair u = first norm
-    over the regions per word, p = softmax_w(lambda_s u), num_r = sum_w p a, q_r = p_r^T H_c p_r (clamped at 0, :112),
-    s_r = num_r / max(||v_r|| sqrt(q_r), 1e-8) (:115)."""
+    """scan_train_i2t.hip:3-9 (header), :52-59 (i2t_pair_forward) and scan_train_pair.h:63-134 (pair_forward with context = words,
+    query = regions): A = V E^T, H_c = E_c E_c^T, ||v_r||; per pair u = first norm over the regions per word,
+    p = softmax_w(lambda_s u), num_r = sum_w p a, q_r = p_r^T H_c p_r (clamped at 0, scan_train_pair.h:129),
+    s_r = num_r / max(||v_r|| sqrt(q_r), 1e-8) (:131)."""
     V, E = x['images'], x['words']
     Bi, R, D = V.shape
-    A = (V.reshape(Bi * R, D) @ E.t()).view(Bi, R, -1)               # autograd.py: _ScanI2T.forward
-    vnorm = (V * V).sum(2).sqrt()                                      # scan_train_i2t.hip:276-284
+    A = (V.reshape(Bi * R, D) @ E.t()).view(Bi, R, -1)               # autograd.py: _scan_pair_dots
+    vnorm = (V * V).sum(2).sqrt()                                      # scan_train.hip:180-188 (rownorm_train_kernel)
     cols = []
     for o, W in zip(_offsets(lens), lens):
         Ec = E[o:o + W]
-        H = Ec @ Ec.t()                                                # scan_train_i2t.hip:288-324
+        H = Ec @ Ec.t()                                                # scan_train_i2t.hip:113-149
         a = A[:, :, o:o + W]
         p = torch.softmax(LAMBDA_SOFTMAX * _first_norm(a, norm, 1), 2)
         num = (p * a).sum(2)
@@ -417,7 +418,7 @@ _seam('t2i', **{'R*W': ('<256', '=256', '>256')})
 I2T_ROUTES = {
     (SC_R, True): ((36, 1), (36, 2), (36, 16), (36, 17), (36, 64), (36, 65), (36, 96)),
     (SC_R, False): ((1, 96), (35, 1), (1, 2), (35, 16), (16, 17), (35, 64), (1, 65)),
-    (SI_RMAX, False): ((37, 1), (100, 96), (37, 2), (100, 16), (49, 17), (37, 64), (100, 65)),
+    (ST_RMAX, False): ((37, 1), (100, 96), (37, 2), (100, 16), (49, 17), (37, 64), (100, 65)),
 }
 for _i, (_route, _shapes) in enumerate(I2T_ROUTES.items()):
     for _j, (_R, _W) in enumerate(_shapes):
@@ -426,8 +427,8 @@ for _i, (_route, _shapes) in enumerate(I2T_ROUTES.items()):
 _seam('i2t', R=(1, 35, 36, 37, 100), W=(1, 2, 16, 17, 64, 65, 96), fwd_route=list(I2T_ROUTES), bwd_route=list(I2T_ROUTES),
       **{'R,W': ((100, 96),), 'W*W': (256, 289)})
 
-# the feature axis: 32-wide slices of caption_gram_kernel (zero-filled tail), the rownorm kernels' lane stride of 64, the 256-wide
-# grids of scan_train_gram_bwd_kernel / enorm_bwd_kernel / rowscale_add_kernel and i2t_gram_bwd_kernel's stride of 256; the three
+# the feature axis: 32-wide slices of caption_gram_kernel (zero-filled tail), the rownorm kernel's lane stride of 64, the 256-wide
+# grids of scan_train_gram_bwd_kernel / rownorm_bwd_kernel (both directions) and i2t_gram_bwd_kernel's stride of 256; the three
 # region classes of the Gram backward at D > 256; Bi <= 2
 SCAN_D = (1, 31, 32, 33, 62, 63, 64, 65, 255, 256, 257, 513)
 for _xa, _ls in (('t2i', (3, 1, 6)), ('i2t', (17, 16, 2))):
@@ -450,7 +451,7 @@ for _Bc in SCAN_BC:
 _seam('t2i', Bc=SCAN_BC, dg_reduce_blocks=(1, 2), **{'R*R': (256, 289)})
 _seam('i2t', Bc=SCAN_BC)
 
-# images per batch; region rows Bi * R that are no multiple of the rownorm kernels' four rows per workgroup (i2t)
+# images per batch; region rows Bi * R that are no multiple of the rownorm kernel's four rows per workgroup (i2t)
 SCAN_BI = (1, 2, 5)
 for _Bi in SCAN_BI:
     _add('Bi', 't2i', _Bi, 36, 20, (3, 1, 4), *_rot('t2i'))

@@ -174,13 +174,20 @@ def _src(*path):
 def test_constants_are_the_ones_of_the_source():
     """The mirrors' constants and gates, as the source text states them (whitespace folded)."""
     text = {"scan_train.hip": _src("csrc", "scan_train.hip"), "scan_train_i2t.hip": _src("csrc", "scan_train_i2t.hip"),
-            "scan_common.h": _src("csrc", "scan_common.h"), "autograd.py": _src("itr_amd", "autograd.py"), "ops.py": _src("itr_amd", "ops.py")}
+            "scan_train_pair.h": _src("csrc", "scan_train_pair.h"), "scan_common.h": _src("csrc", "scan_common.h"),
+            "autograd.py": _src("itr_amd", "autograd.py"), "ops.py": _src("itr_amd", "ops.py")}
     pins = {
         "scan_common.h": ("constexpr int SC_R = %d;" % S.SC_R,),
-        "scan_train.hip": (
+        "scan_train_pair.h": (     # what both directions share
             "constexpr int ST_RMAX = %d;" % S.ST_RMAX, "constexpr int ST_MAXW = %d;" % S.ST_MAXW,
-            # check_train_args and the two launchers
+            # check_train_args
             "ITR_UNSUPPORTED(R < 1 || R > ST_RMAX,", "ITR_UNSUPPORTED(max_len > ST_MAXW,",
+            # the arithmetic the mirrors copy
+            "q = fmaxf(q, 0.f);", "sm.s[k] = sm.num[k] / fmaxf(qnorm[k] * sqrtf(q), 1e-8f);",
+            "const float rn = (l2 || l1) ? 1.f / (st + 1e-8f) : (norm == 2 ? 1.f / st : 1.f);",
+        ),
+        "scan_train.hip": (
+            # the two launchers
             "const bool w64 = max_len <= 64;",
             "if (R == SC_R && max_len <= 32) return launch_pair<PairSmem<32, SC_R>>(scan_train_fwd_kernel<32, SC_R, true>,",
             "if (R == SC_R && max_len <= 32) return launch_pair<PairBwdSmem<32, SC_R>>(scan_train_bwd_dense_kernel<32, SC_R, true>,",
@@ -195,30 +202,36 @@ def test_constants_are_the_ones_of_the_source():
             "for (; c + %d <= Bc; c += %d) {" % (S.DG_UNROLL, S.DG_UNROLL), "float v[%d];" % S.DG_UNROLL,
             "hipLaunchKernelGGL(scan_train_dg_reduce_kernel, dim3((unsigned)ceil_div(R * R, 256), (unsigned)Bi), dim3(256),",
             "const dim3 gb((unsigned)ceil_div(D, 256), (unsigned)Bi);",
-            "hipLaunchKernelGGL(enorm_bwd_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)n_tok), dim3(256),",
-            # the arithmetic the mirror copies
-            "q = fmaxf(q, 0.f);", "sm.s[w] = sm.num[w] / fmaxf(g.enorm[off + w] * sqrtf(q), 1e-8f);",
-            "const float rn = (l2 || l1) ? 1.f / (st + 1e-8f) : (g.norm == 2 ? 1.f / st : 1.f);",
+            "hipLaunchKernelGGL(rownorm_bwd_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)n_tok), dim3(256),",
+            # the query norm of the shared arithmetic: ||e_w||
+            "pair_forward<true>(sm, R, W, g.enorm + off, g.norm, g.ls);",
         ),
         "scan_train_i2t.hip": (
-            "constexpr int SI_RMAX = %d;" % S.SI_RMAX, "constexpr int SI_MAXW = %d;" % S.SI_MAXW,
-            "ITR_UNSUPPORTED(R < 1 || R > SI_RMAX,", "ITR_UNSUPPORTED(max_len > SI_MAXW,",
-            "if (R == SC_R) return launch_i2t<SC_R>(scan_train_i2t_fwd_kernel<SC_R, true>,",
-            "if (R < SC_R) return launch_i2t<SC_R>(scan_train_i2t_bwd_kernel<SC_R, false>,",
-            "return launch_i2t<SI_RMAX>(scan_train_i2t_bwd_kernel<SI_RMAX, false>,",
+            "ITR_UNSUPPORTED(R < 1 || R > ST_RMAX,", 'check_train_args("itr_scan_train_i2t_fwd",', 'check_train_args("itr_scan_train_i2t_bwd",',
+            "if (R == SC_R) return launch_pair<I2TSmem<SC_R>>(scan_train_i2t_fwd_kernel<SC_R, true>,",
+            "if (R < SC_R) return launch_pair<I2TSmem<SC_R>>(scan_train_i2t_bwd_kernel<SC_R, false>,",
+            "return launch_pair<I2TSmem<ST_RMAX>>(scan_train_i2t_bwd_kernel<ST_RMAX, false>,",
             # caption_gram_kernel's slices, the row kernels' geometry
-            "__shared__ float xs[SI_MAXW][%d];" % (S.CGRAM_SLICE + 1), "for (int k0 = 0; k0 < D; k0 += %d) {" % S.CGRAM_SLICE,
-            "constexpr int NP = (SI_MAXW * SI_MAXW + 255) / 256;",
-            "hipLaunchKernelGGL(rownorm_i2t_kernel, dim3((unsigned)ceil_div(Bi * R, 4)), dim3(256),",
+            "__shared__ float xs[ST_MAXW][%d];" % (S.CGRAM_SLICE + 1), "for (int k0 = 0; k0 < D; k0 += %d) {" % S.CGRAM_SLICE,
+            "constexpr int NP = (ST_MAXW * ST_MAXW + 255) / 256;",
+            "hipLaunchKernelGGL(rownorm_train_kernel, dim3((unsigned)ceil_div(Bi * R, 4)), dim3(256),",
             "for (int d = threadIdx.x; d < D; d += 256) {",
-            "hipLaunchKernelGGL(rowscale_add_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)(Bi * R)), dim3(256),",
-            "sm.s[r] = num / fmaxf(g.vnorm[i * R + r] * sqrtf(q), 1e-8f);",
+            "hipLaunchKernelGGL(rownorm_bwd_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)(Bi * R)), dim3(256),",
+            # the query norm of the shared arithmetic: ||v_r||
+            "pair_forward<false>(sm, W, R, g.vnorm + i * R, g.norm, g.ls);",
         ),
-        "autograd.py": ("ntp = (n_tok + %d) // %d * %d" % (S.NTP_ROUND - 1, S.NTP_ROUND, S.NTP_ROUND),),
+        "autograd.py": ("ntp = (n_tok + %d) // %d * %d" % (S.NTP_ROUND - 1, S.NTP_ROUND, S.NTP_ROUND),
+                        'V2, Ep, A, (Bi, Bc, n_tok, ntp, R, D) = _scan_pair_dots("scan_t2i_scores", V, E, cap_len)',
+                        'V2, Ep, A, (Bi, Bc, n_tok, ntp, R, D) = _scan_pair_dots("scan_i2t_scores", V, E, cap_len)'),
         "ops.py": ("return t.contiguous()",),
     }
     for name, lines in pins.items():
         for line in lines:
             assert line in text[name], "%s no longer says: %s" % (name, line)
-    assert text["autograd.py"].count(pins["autograd.py"][0]) == 2             # _ScanT2I.forward and _ScanI2T.forward
-    assert text["scan_train.hip"].count("for (int d = lane; d < D; d += 64)") == 2 and "for (int d = lane; d < D; d += 64)" in text["scan_train_i2t.hip"]
+    # one copy of what the directions share: the padding rule (_scan_pair_dots), the constants, the checks and the row-norm kernel
+    assert text["autograd.py"].count(pins["autograd.py"][0]) == 1
+    for name in ("scan_train.hip", "scan_train_i2t.hip"):
+        assert "constexpr int ST_" not in text[name] and "constexpr int SI_" not in text[name] and "static int check" not in text[name], name
+    lane_loop = "for (int d = lane; d < D; d += 64)"
+    assert text["scan_train.hip"].count(lane_loop) == 2 and lane_loop not in text["scan_train_i2t.hip"]     # the Gram kernel and the row norms
+    assert sum(t.count("void rownorm_train_kernel(") + t.count("void rownorm_bwd_kernel(") for t in text.values()) == 2

@@ -108,20 +108,21 @@ def oracle_cpu_step(model_name, batch, cfg, model=None):
     wt = {'embed.weight': torch.empty(V_COCO, E).uniform_(-0.1, 0.1)}
     wt.update({'rnn.' + k: v.detach() for k, v in rnn.state_dict().items()})
     feats, ids, lens = batch[0].cpu(), batch[3].cpu(), batch[4]
-    ocfg = dict(bi_gru=True, margin=0.2, max_violation=True, learning_rate=2e-4, grad_clip=2.0, cross_attn='t2i', raw_feature_norm='clipped_l2norm',
+    ocfg = dict(bi_gru=True, margin=0.2, max_violation=True, learning_rate=2e-4, grad_clip=2.0, cross_attn=cfg['cross_attn'], raw_feature_norm='clipped_l2norm',
                 agg_func='LogSumExp', lambda_lse=6.0, lambda_softmax=9.0)
     t0 = time.perf_counter()
     O.gru_model_train_step(kind, wi, wt, feats, ids, lens, ocfg)
     return time.perf_counter() - t0
 
 
-def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=None, mask_same_image=False):
+def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=None, mask_same_image=False, cross_attn='t2i'):
     from itr_amd import config as C
     from itr_amd.modalmodule import get_model
     from itr_amd.metricmodule.evaluation import LogCollector
     dev = dev or torch.device("cuda", 0)
     cfg = C.build_config(['with', model_name, 'data_name=coco_precomp', 'bi_gru=True', 'max_violation=True',
-                          'mask_same_image=%s' % bool(mask_same_image)] + (['module_name=' + module] if model_name == 'SGRAF' else []))
+                          'mask_same_image=%s' % bool(mask_same_image)] + (['module_name=' + module] if model_name == 'SGRAF' else [])
+                         + (['cross_attn=' + cross_attn] if model_name == 'SCAN' else []))
     cfg['vocab_size'] = V_COCO
     cfg['img_dim'] = 2048        # precomp region features
     if model_name in ('SAEM', 'CAMERA'):
@@ -218,6 +219,7 @@ def main():
     ap.add_argument("--cpu", action="store_true", help="time the oracle's training step on the host cores beside VSE++ / SCAN")
     ap.add_argument("--budget", type=float, default=1e9, help="--all: seconds after which no further family is started")
     ap.add_argument("--mask-same-image", action="store_true", help="time the step with mask_same_image=True (the hinge with the group mask)")
+    ap.add_argument("--cross-attn", default="t2i", choices=["t2i", "i2t"], help="SCAN: the direction of the cross attention")
     a = ap.parse_args()
     t_start = time.perf_counter()
     rows = {}
@@ -228,7 +230,7 @@ def main():
             rows[name] = {"error": "not started: the time budget of the run was spent"}
             continue
         try:
-            r = run(model_name, module, a.batch or batch, a.steps, a.warmup, cpu=a.cpu, mask_same_image=a.mask_same_image)
+            r = run(model_name, module, a.batch or batch, a.steps, a.warmup, cpu=a.cpu, mask_same_image=a.mask_same_image, cross_attn=a.cross_attn)
         except Exception as e:      # noqa: BLE001  (one family must not take the others' rows with it)
             r = {"family": name, "error": "%s: %s" % (type(e).__name__, e)}
         rows[name] = r
