@@ -107,7 +107,8 @@ extern "C" int itr_camera_posenc(const float *boxes, const float *imgs_wh, float
 
 extern "C" int itr_camera_summarize(const float *smry, const float *X, float *out, int64_t B, int R, int k, int D,
                                     itr_stream_t stream) {
-    ITR_REQUIRE(smry && X && out && B >= 0 && R >= 1 && R <= 64 && k >= 1 && D >= 1, "itr_camera_summarize: bad argument");
+    ITR_REQUIRE(smry && X && out && B >= 0 && R >= 1 && k >= 1 && D >= 1, "itr_camera_summarize: bad argument");
+    ITR_UNSUPPORTED(R > 64, "itr_camera_summarize: at most 64 regions per image (got %d)", R);
     ITR_REQUIRE(B * k < 0x7fffffffLL, "itr_camera_summarize: grid too large");
     if (B == 0) return ITR_OK;
     hipLaunchKernelGGL(itr::summarize_kernel, dim3((unsigned)(B * k)), dim3(256), 0, itr::as_stream(stream), smry, X, R, k, D, out);

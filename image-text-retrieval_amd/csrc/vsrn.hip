@@ -99,7 +99,8 @@ __global__ __launch_bounds__(256) void gcn_relation_kernel(const float *__restri
 
 extern "C" int itr_gcn_relation(const float *tpg, int64_t ld, float *y, int64_t ldy, int64_t n_img, int N, int D,
                                 itr_stream_t stream) {
-    ITR_REQUIRE(n_img >= 0 && N >= 1 && N <= itr::GCN_MAXN && D >= 1, "itr_gcn_relation: bad shape (at most 36 regions)");
+    ITR_REQUIRE(n_img >= 0 && N >= 1 && D >= 1, "itr_gcn_relation: bad shape");
+    ITR_UNSUPPORTED(N > itr::GCN_MAXN, "itr_gcn_relation: at most %d regions per image (got %d)", itr::GCN_MAXN, N);
     if (n_img == 0) return ITR_OK;
     ITR_REQUIRE(tpg && y, "itr_gcn_relation: null pointer");
     ITR_REQUIRE(ld >= 3 * (int64_t)D && ldy >= D && ld % 4 == 0 && D % 4 == 0, "itr_gcn_relation: strides (ld >= 3 D, multiples of 4)");

@@ -48,7 +48,8 @@ int itr_l2norm_rows(const float *x, float *y, int64_t rows, int dim, float eps, 
                     int take_abs, itr_stream_t stream);
 
 /* y[b,:] = mean_r x[b,r,:] for x [B,R,F]  (torch.mean(x, 1): Fusionmodule.py:412,422; TextEncoder.py:191;
- * ImgEncoder.py:348; the VSE++ region pooling of SURVEY Q3). */
+ * ImgEncoder.py:348; the VSE++ region pooling of SURVEY Q3).  At most 65535 groups per call; x and y 16-byte aligned when F % 4 == 0
+ * (the float4 path), any alignment otherwise. */
 int itr_mean_mid(const float *x, float *y, int64_t B, int R, int F, itr_stream_t stream);
 
 /* ---- measure='order' (config.py:74): order_sim, Objectives.py:24-30 ----------------------
@@ -68,7 +69,7 @@ int itr_pdist_finish(float *S, const float *n1, const float *n2, int64_t Ni, int
  * (itr/modalmodule/vsrn_.py:50-71).  tpg [n_img*N, ld]: per region row the three convolution outputs side by side,
  * theta at columns [0, D), phi at [D, 2D), g at [2D, 3D) (one GEMM with the stacked weight).  For every image
  *   y[n, :] = sum_m (theta[n,:] . phi[m,:] / N) g[m, :]           (R = theta_v phi_v^T; R_div_C = R / N; y = R_div_C g_v)
- * y [n_img*N, ldy].  N <= 36 regions, D and ld multiples of 4. */
+ * y [n_img*N, ldy].  N <= 36 regions (more: ITR_ERR_UNSUPPORTED), D and ld multiples of 4. */
 int itr_gcn_relation(const float *tpg, int64_t ld, float *y, int64_t ldy, int64_t n_img, int N, int D,
                      itr_stream_t stream);
 
@@ -267,7 +268,8 @@ int itr_relu_maxpool(const float *x, float *out, int64_t ldo, int64_t B, int L, 
  *                       [rows, dk] (dk = 16 or 32; other head sizes: compose itr_gemm_nt + itr_mul_rows),  G = fc_q(q) * fc_k(k),
  *                       M = sigmoid(fc_g(G)) [rows, 2 dk],  q_out = q * M[:, :dk],  k_out = k * M[:, dk:]  (outputs may alias inputs)
  * itr_camera_posenc   : absoluteEncode(boxes, imgs_wh) -> [B*R, 6]   (:118-128)
- * itr_camera_summarize: softmax over regions of smry[B,R,k], L^T X, F.normalize -> [B,k,D]  (ImgEncoder.py:385-389) */
+ * itr_camera_summarize: softmax over regions of smry[B,R,k], L^T X, F.normalize -> [B,k,D]  (ImgEncoder.py:385-389); R <= 64
+ *                       (more: ITR_ERR_UNSUPPORTED) */
 int itr_gemm_nt_acc(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, float *C,
                     int64_t ldc, int64_t M, int64_t N, int64_t K, int act, itr_stream_t stream);
 /* C = act(R + A B^T + bias): itr_gemm_nt_acc with the summand read from its own matrix (Rs_GCN's `W(y) + v`, vsrn_.py:64-67: no
