@@ -32,7 +32,11 @@ DEFAULTS = dict(
     resident_data=False,
     # not a key of the reference: True keeps two captions of the same image in a batch from being mined as each other's
     # negatives (ops.hinge_loss(groups=ids // im_div)); False is the reference's loss, which masks the diagonal only
-    mask_same_image=False)
+    mask_same_image=False,
+    # not keys of the reference: the ranking loss of training, 'hinge' (the reference's, with margin / max_violation) or 'infonce'
+    # (softmax contrastive loss on scores / temperature, ops.infonce_loss).  Training switches like mask_same_image:
+    # not in load_hyperparams, and model code reads them with .get so that configurations of old checkpoints still load
+    loss='hinge', temperature=0.05)
 
 NAMED = {
     'VSE_PP': dict(name="VSE++", data_name="f30k_precomp", vocab_type='pkl', val_step=10, img_dim=4096,

@@ -28,6 +28,7 @@ class base_module(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
+        Objectives.retrieval_loss_kind(config)      # an unknown config['loss'] is refused here, when the model is built
         self.grad_clip = config.get('grad_clip', 2.)
         self.Eiters = 0
         self.img_enc = None
@@ -114,7 +115,10 @@ class base_module(nn.Module):
         return images, captions, lens, rows, toks, lens_all
 
     def _hinge(self, scores, groups):
-        """The retrieval hinge of a training step; `groups` from _hinge_groups (None: exactly the reference's call)."""
+        """The retrieval loss of a training step; `groups` from _hinge_groups (None: exactly the reference's call).
+        config['loss'] = 'infonce' puts the softmax contrastive loss in the hinge's place, on the same matrix and groups."""
+        if Objectives.retrieval_loss_kind(self.config) == 'infonce':
+            return ops.infonce_loss(scores, self.config.get('temperature', 0.05), groups=groups)
         if groups is None:
             return ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'])
         return ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'], groups=groups)
@@ -179,8 +183,7 @@ class VSE_PP(base_module):
                                                use_abs=config['use_abs'], no_txtnorm=False, method_name='VSE++')
         self.img_enc.cuda()
         self.txt_enc.cuda()
-        self.criterion = Objectives.ContrastiveLoss(config=config, margin=config['margin'],
-                                                    max_violation=config['max_violation'], measure=config['measure'])
+        self.criterion = Objectives.make_criterion(config)
         self.params = list(self.txt_enc.parameters()) + list(self.img_enc.fc.parameters())
         self.optimizer = ag.Adam(self.params, lr=config['learning_rate'])
         self.calculate_params()
@@ -233,9 +236,7 @@ class SCAN(base_module):
                                                no_txtnorm=config['no_txtnorm'])
         self.img_enc.cuda()
         self.txt_enc.cuda()
-        self.criterion = Objectives.ContrastiveLoss(config=config, margin=config['margin'],
-                                                    measure=config['measure'],
-                                                    max_violation=config['max_violation'])
+        self.criterion = Objectives.make_criterion(config)
         self.params = list(self.txt_enc.parameters()) + list(self.img_enc.fc.parameters())
         self.optimizer = ag.Adam(self.params, lr=config['learning_rate'])
         self.calculate_params()
@@ -307,8 +308,7 @@ class VSRN(base_module):
         self.img_enc.cuda()
         self.txt_enc.cuda()
         self.caption_model.cuda()
-        self.criterion = Objectives.ContrastiveLoss(config=config, margin=config['margin'], measure=config['measure'],
-                                                    max_violation=config['max_violation'])
+        self.criterion = Objectives.make_criterion(config)
         self.params = list(self.txt_enc.parameters()) + list(self.img_enc.parameters()) + list(self.caption_model.parameters())
         self.calculate_params()
 
@@ -407,8 +407,7 @@ class SGRAF(base_module):
         self.img_enc.cuda()
         self.txt_enc.cuda()
         self.sim_enc.cuda()
-        self.criterion = Objectives.ContrastiveLoss(config=config, margin=config['margin'], measure=config['measure'],
-                                                    max_violation=config['max_violation'])
+        self.criterion = Objectives.make_criterion(config)
         self.params = list(self.txt_enc.parameters()) + list(self.img_enc.parameters()) + list(self.sim_enc.parameters())
         self.calculate_params()
 
@@ -470,8 +469,7 @@ class SAEM(base_module):
         self.txt_enc = TextEncoder.BertMapping(config)
         self.txt_enc.cuda()
         self.img_enc.cuda()
-        self.criterion = Objectives.ContrastiveLoss(config=config, margin=config['margin'], measure=config['measure'],
-                                                    max_violation=config['max_violation'])
+        self.criterion = Objectives.make_criterion(config)
         self.criterion_2 = Objectives.AngularLoss()
         self.params = list(self.txt_enc.parameters()) + list(self.img_enc.parameters())
         self.calculate_params()
@@ -567,7 +565,7 @@ class CAMERA(base_module):
         self.mvm = Fusionmodule.MultiViewMatching()
         self.img_enc.cuda()       # one process per GPU: no nn.DataParallel wrapper (Models.py:561-562)
         self.txt_enc.cuda()
-        self.crit_ranking = Objectives.TripletLoss(margin=config['margin'], max_violation=config['max_violation'])
+        self.crit_ranking = Objectives.make_scores_criterion(config)
         self.crit_div = Objectives.DiversityRegularization(config['smry_k'], config['batch_size'])
         self.params = list(self.txt_enc.parameters()) + list(self.img_enc.parameters())
         self.calculate_params()

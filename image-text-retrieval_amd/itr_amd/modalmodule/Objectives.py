@@ -52,15 +52,13 @@ def xattn_score_i2t(images, captions, cap_lens, config):
     return _xattn(images, captions, cap_lens, config, 'i2t')
 
 
-class ContrastiveLoss(nn.Module):
-    """Bidirectional hinge loss, optionally with hardest negatives (Objectives.py:34-115).
-    `self.sim` is dispatched on config['name'] exactly like the reference (:45-74)."""
+class _PairSimilarity(nn.Module):
+    """The similarity of a ranking criterion: `self.sim` dispatched on config['name'] exactly like the reference's ContrastiveLoss
+    (Objectives.py:45-74), and the same measures on the autograd tape.  Shared by ContrastiveLoss and InfoNCELoss."""
 
-    def __init__(self, config, margin=0, measure=None, max_violation=False):
+    def __init__(self, config, measure=None):
         super().__init__()
         self.config = config
-        self.margin = margin
-        self.max_violation = max_violation
         if measure == 'order':
             self.sim = order_sim
         elif measure == 'cosine':
@@ -98,16 +96,73 @@ class ContrastiveLoss(nn.Module):
             raise NotImplementedError("SAEM's loss terms are composed in SAEM.forward_loss / train_emb")
         return ag.order_scores(im, s) if self.sim is order_sim else ag.cosine_scores(im, s)
 
+    def _scores(self, im, s, s_l):
+        if torch.is_grad_enabled() and (im.requires_grad or (torch.is_tensor(s) and s.requires_grad)):
+            return self._sim_on_tape(im, s, s_l)
+        return self.sim(im, s, s_l, self.config)
+
+
+class ContrastiveLoss(_PairSimilarity):
+    """Bidirectional hinge loss, optionally with hardest negatives (Objectives.py:34-115)."""
+
+    def __init__(self, config, margin=0, measure=None, max_violation=False):
+        super().__init__(config, measure)
+        self.margin = margin
+        self.max_violation = max_violation
+
     def forward(self, im, s=None, s_l=None, groups=None):
         """`groups` (one integer per pair, e.g. the image id): pairs of one group are no negatives of each other (ops.hinge_loss);
         None is the reference's loss."""
-        if torch.is_grad_enabled() and (im.requires_grad or (torch.is_tensor(s) and s.requires_grad)):
-            scores = self._sim_on_tape(im, s, s_l)
-        else:
-            scores = self.sim(im, s, s_l, self.config)
+        scores = self._scores(im, s, s_l)
         if groups is None:
             return ops.hinge_loss(scores, self.margin, self.max_violation)
         return ops.hinge_loss(scores, self.margin, self.max_violation, groups=groups)
+
+
+class InfoNCELoss(_PairSimilarity):
+    """Softmax contrastive loss (ops.infonce_loss) on the similarity ContrastiveLoss would use for this configuration.  Not a loss of
+    the reference: config['loss'] = 'infonce' selects it."""
+
+    def __init__(self, config, temperature, measure=None):
+        super().__init__(config, measure)
+        self.temperature = temperature
+
+    def forward(self, im, s=None, s_l=None, groups=None):
+        """`groups` as in ContrastiveLoss.forward: pairs of one group are left out of each other's softmax."""
+        return ops.infonce_loss(self._scores(im, s, s_l), self.temperature, groups=groups)
+
+
+class InfoNCEScoresLoss(nn.Module):
+    """InfoNCE on a given score matrix: TripletLoss's place in CAMERA when config['loss'] = 'infonce'."""
+
+    def __init__(self, temperature):
+        super().__init__()
+        self.temperature = temperature
+
+    def forward(self, scores, groups=None):
+        return ops.infonce_loss(scores, self.temperature, groups=groups)
+
+
+def retrieval_loss_kind(config):
+    """config['loss'] ('hinge' when the key is absent: a configuration from an old checkpoint), checked."""
+    kind = config.get('loss', 'hinge')
+    if kind not in ('hinge', 'infonce'):
+        raise ValueError("unknown loss %r (known: 'hinge', 'infonce')" % (kind,))
+    return kind
+
+
+def make_criterion(config):
+    """The ranking criterion of a model family: ContrastiveLoss, or InfoNCELoss when config['loss'] says so."""
+    if retrieval_loss_kind(config) == 'infonce':
+        return InfoNCELoss(config=config, temperature=config.get('temperature', 0.05), measure=config['measure'])
+    return ContrastiveLoss(config=config, margin=config['margin'], measure=config['measure'], max_violation=config['max_violation'])
+
+
+def make_scores_criterion(config):
+    """CAMERA's criterion on a given score matrix: TripletLoss, or InfoNCE when config['loss'] says so."""
+    if retrieval_loss_kind(config) == 'infonce':
+        return InfoNCEScoresLoss(config.get('temperature', 0.05))
+    return TripletLoss(margin=config['margin'], max_violation=config['max_violation'])
 
 
 class TripletLoss(nn.Module):

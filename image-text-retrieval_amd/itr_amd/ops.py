@@ -423,6 +423,90 @@ def hinge_loss(scores, margin=0.2, max_violation=False, groups=None):
     return _HingeGroupsFn.apply(scores, margin, max_violation, _hinge_groups(groups, scores.shape[0], scores.device))
 
 
+def _infonce_scale(temperature):
+    """float32(1 / temperature), the factor the kernels multiply the scores by."""
+    t = float(temperature)
+    if not np.isfinite(t) or t <= 0.0:
+        raise ValueError("InfoNCE loss: temperature must be finite and positive, got %r" % (temperature,))
+    with np.errstate(over='ignore', under='ignore'):
+        scale = float(np.float32(1.0 / t))
+    if not np.isfinite(scale) or scale <= 0.0:
+        raise ValueError("InfoNCE loss: 1 / temperature does not fit float32 for temperature %r" % (temperature,))
+    return scale
+
+
+def _infonce_scores(scores):
+    scores = _dev(scores, name="scores")
+    if scores.dim() != 2 or scores.shape[0] != scores.shape[1]:
+        raise ValueError("InfoNCE loss needs a square score matrix, got %s" % (tuple(scores.shape),))
+    return scores
+
+
+def infonce_fwd(scores, temperature=0.05, groups=None):
+    """-> (loss[1], row_lse[B], col_lse[B]) of the softmax contrastive loss on z = scores / temperature (itr_infonce_fwd): the mean over
+    the B rows and the B columns of log-sum-exp minus the diagonal.  `groups` (length B, integers): entries (i, j), i != j, of one group
+    are left out of both sums, the rule of hinge_fwd; None masks nothing."""
+    lib = _lib.load()
+    scores = _infonce_scores(scores)
+    scale = _infonce_scale(temperature)
+    B = scores.shape[0]
+    if groups is not None:
+        groups = _hinge_groups(groups, B, scores.device)
+    loss = torch.empty(1, device=scores.device, dtype=torch.float32)
+    row_lse = torch.empty(B, device=scores.device, dtype=torch.float32)
+    col_lse = torch.empty(B, device=scores.device, dtype=torch.float32)
+    ws = torch.empty(max(1, int(lib.itr_infonce_workspace_bytes(B))), device=scores.device, dtype=torch.uint8)
+    _lib.check(lib.itr_infonce_fwd(_p(scores), _p(groups), B, B, scale, _p(loss), _p(row_lse), _p(col_lse), _p(ws), _stream()))
+    return loss, row_lse, col_lse
+
+
+def infonce_bwd(scores, temperature, row_lse, col_lse, grad_loss, groups=None):
+    """dS of infonce_fwd from its saved log-sum-exps (itr_infonce_bwd); exactly 0 at masked entries."""
+    lib = _lib.load()
+    scores = _infonce_scores(scores)
+    scale = _infonce_scale(temperature)
+    B = scores.shape[0]
+    if groups is not None:
+        groups = _hinge_groups(groups, B, scores.device)
+    g = _dev(grad_loss.reshape(1), name="grad_loss")
+    row_lse, col_lse = _dev(row_lse, name="row_lse"), _dev(col_lse, name="col_lse")
+    if row_lse.shape != (B,) or col_lse.shape != (B,):
+        raise ValueError("InfoNCE loss: row_lse and col_lse must have length %d" % B)
+    dS = torch.empty_like(scores)
+    _lib.check(lib.itr_infonce_bwd(_p(scores), _p(groups), B, B, scale, _p(row_lse), _p(col_lse), _p(g), _p(dS), B, _stream()))
+    return dS
+
+
+class _InfoNCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, temperature, groups):
+        scores = scores.contiguous()
+        loss, row_lse, col_lse = infonce_fwd(scores, temperature, groups)
+        if groups is None:
+            ctx.save_for_backward(scores, row_lse, col_lse)
+        else:
+            ctx.save_for_backward(scores, row_lse, col_lse, groups)
+        ctx.temperature = temperature
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad):
+        scores, row_lse, col_lse = ctx.saved_tensors[:3]
+        groups = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        return infonce_bwd(scores, ctx.temperature, row_lse, col_lse, grad.contiguous(), groups), None, None
+
+
+def infonce_loss(scores, temperature=0.05, groups=None):
+    """Differentiable (w.r.t. scores) InfoNCE loss, HIP forward and backward: image-to-text and text-to-image softmax cross-entropy on
+    scores / temperature with the diagonal as the positive, averaged.  `groups` as in hinge_loss: pairs of one group -- captions of
+    the same image -- are not each other's negatives."""
+    scores = _infonce_scores(scores)
+    _infonce_scale(temperature)
+    if groups is not None:
+        groups = _hinge_groups(groups, scores.shape[0], scores.device)
+    return _InfoNCEFn.apply(scores, temperature, groups)
+
+
 # ------------------------------------------------------------------------------------------
 class ScanPlan:
     """Column-tile plan of a caption set for the SCAN kernel (host-side, cheap, reusable).

@@ -201,6 +201,30 @@ int itr_hinge_groups_bwd(const float *S, const int32_t *group, int B, int64_t ld
                          const int32_t *row_arg, const int32_t *col_arg, const float *grad_loss,
                          float *dS, int64_t lddS, itr_stream_t stream);
 
+/* ---- InfoNCE (softmax contrastive) loss on the same B x B matrix: row i is image i, column j caption j, the positive is the
+ * diagonal.  The entry stands next to ContrastiveLoss.forward (Objectives.py:93-115) and replaces no reference line.
+ *   scale = float32(1 / temperature), z = scale * S (one fp32 product).
+ *   group[B] (int32, device; any values) or NULL = no mask: an off-diagonal entry (i, j) with group[i] == group[j] is MASKED, the
+ *   rule of itr_hinge_groups_*.  A(i) = {i} u {j : group[j] != group[i]}; the mask is symmetric, so A(i) serves row i and column i.
+ *     row_lse[i] = log sum_{j in A(i)} exp(z[i,j])        col_lse[j] = log sum_{i in A(j)} exp(z[i,j])
+ *     loss = ( sum_i (row_lse[i] - z[i,i]) + sum_j (col_lse[j] - z[j,j]) ) / (2 B)
+ *     dS[i,j] = g * scale / (2 B) * ( exp(z[i,j] - row_lse[i]) + exp(z[i,j] - col_lse[j]) - 2 [i == j] )   for j in A(i)
+ *     dS[i,j] = 0 exactly at masked entries;  g = grad_loss[0] (device scalar, as in the hinge).
+ *   B = 1 gives loss 0 and dS 0; a row whose negatives are all masked contributes 0.
+ * fwd writes loss[0], row_lse[B] and col_lse[B] (fp32, kept for the backward) and needs itr_infonce_workspace_bytes(B) bytes of
+ * scratch; bwd makes one pass that writes every entry of dS once, zeros at masked entries included.  Every log-sum-exp subtracts
+ * its running maximum; masked entries are skipped, not turned into -inf arithmetic.  Deterministic: no float atomics, the 2B terms
+ * are summed in a fixed order, two runs give the same bits, and all-distinct groups give the bits of group == NULL.  S is read in
+ * whole 256-byte row segments by the row pass and by the column pass alike.  B is not limited to a multiple of anything.
+ * Host checks before anything touches the device (ITR_ERR_BADARG, "itr_infonce_fwd: ..." / "itr_infonce_bwd: ..."): null S /
+ * loss / row_lse / col_lse / workspace / grad_loss / dS, B < 1, ldS < B, lddS < B, scale not finite or <= 0.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+size_t itr_infonce_workspace_bytes(int B);
+int itr_infonce_fwd(const float *S, const int32_t *group /* or NULL */, int B, int64_t ldS, float scale, float *loss,
+                    float *row_lse, float *col_lse, void *workspace, itr_stream_t stream);
+int itr_infonce_bwd(const float *S, const int32_t *group /* or NULL */, int B, int64_t ldS, float scale, const float *row_lse,
+                    const float *col_lse, const float *grad_loss, float *dS, int64_t lddS, itr_stream_t stream);
+
 /* ---- a6: xattn_score_t2i / xattn_score_i2t (Objectives.py:329-476) ---------------------
  * img [Ni,R,D]; words [n_rows,D] with caption c owning rows cap_off[c] .. cap_off[c]+len[c]-1
  * (padded (Nc,L,D) input: cap_off[c] = c*L).  S[i,c] written with row stride ldS.
