@@ -21,7 +21,9 @@
 // (t2i; for i2t the caption Gram H_c = E_c E_c^T plays the same role).  This removes half of
 // the reference's FLOPs (the 2*W*R*D context GEMM and the 3 D-long reductions per word) and all
 // of its HBM traffic for `ctx`; the result differs from the literal evaluation order only by
-// fp32 rounding (tests bound it at 2e-5 absolute on scores in (-1, 1)).
+// fp32 rounding (tests/test_scan_eval_seams_gpu.py bounds the whole score matrix against float64 by 16 x the larger of the float32
+// oracle's own error, the float32 error of this algebra written in plain torch, and 2^-24 max|S|: 1e-6 to 2e-6 on scores in (-1, 1),
+// measured at most 0.2 of that).
 //
 // LDS operand layout (both operands K-contiguous): 8 planes of float4 per 32-wide K chunk,
 // lds[plane][row ^ plane]; see gemm_f32.hip for the bank-conflict argument (the 16x16x4 MFMA
@@ -429,8 +431,11 @@ __device__ __forceinline__ void scan_xattn_body(const ScanArgs &g) {
         float *hbuf = reinterpret_cast<float *>(smem_raw + sizeof(sm.arawt));     // 19 KB of the staging area behind the parked block
         static_assert(sizeof(sm.arawt) + SC_NT * SC_NT * 4 <= sizeof(sm.stage), "caption Gram fits behind the parked block");
         const float *rsim = &sm.rsim2[0][0];
-        // Matrix-core path: every first norm that bounds |b| <= 1 (no max shift needed for exp(ls b), ls <= 60).
-        const bool mfma_path = (norm == 0 || norm == 1 || norm == 2 || norm == 5 || norm == 6) && fabsf(ls) <= 60.f;
+        // Matrix-core path: every first norm that bounds |b| <= 1, while |ls| <= 30.  The path takes no maximum out of exp(ls b), and
+        // ||ctx||^2 = e^T H e holds exp(2 ls b): at 30 that is exp(+-60), which leaves a factor e^28 of float32's range to W * max|H|
+        // above and to ||e_w||^2 below.  (The gate stood at 60 until the seam sweep ran it there: exp(120) is inf, and the scores
+        // came back non-finite once a normalised logit passed 0.74 -- clipped_l2norm reaches that on random inputs.)
+        const bool mfma_path = (norm == 0 || norm == 1 || norm == 2 || norm == 5 || norm == 6) && fabsf(ls) <= 30.f;
         // E1: first normalisation runs along the 36 regions (query axis), per (image, word): lane = word, its 36 raw scores are
         // nine 16-byte reads of the parked column (conflict-free: the 592-byte column pitch puts 16 lanes on 64 distinct banks)
         {

@@ -119,11 +119,11 @@ def _offsets(lens):
     return off
 
 
-def oracle(x, xa, lens, norm, agg):
+def oracle(x, xa, lens, norm, agg, lambda_softmax=LAMBDA_SOFTMAX):
     """itr_oracle.xattn_score on the packed words (padded per caption; the oracle reads captions[c, :len] only)."""
     words, L = x['words'], max(lens)
     cap = torch.stack([torch.nn.functional.pad(words[o:o + w], (0, 0, 0, L - w)) for o, w in zip(_offsets(lens), lens)], 0)
-    return {'S': O.xattn_score(x['images'], cap, list(lens), xa, norm, agg, LAMBDA_LSE, LAMBDA_SOFTMAX)}
+    return {'S': O.xattn_score(x['images'], cap, list(lens), xa, norm, agg, LAMBDA_LSE, lambda_softmax)}
 
 
 def _first_norm(a, norm, dim):
@@ -148,7 +148,7 @@ def _aggregate(s, agg):
     return s.sum(1) if agg == 'Sum' else s.mean(1)
 
 
-def mirror_t2i(x, lens, norm, agg):
+def mirror_t2i(x, lens, norm, agg, lambda_softmax=LAMBDA_SOFTMAX):
     """scan_train.hip:5-14 (header), :73-79 (t2i_pair_forward) and scan_train_pair.h:63-134 (pair_forward with context = regions,
     query = words): A = V E^T for all pairs from one product, G_i = V_i V_i^T, ||e_w||; per pair u = first norm over the caption's
     words per region, p = softmax_r(lambda_s u), num_w = sum_r p a, q_w = p^T G p (clamped at 0, scan_train_pair.h:129),
@@ -161,7 +161,7 @@ def mirror_t2i(x, lens, norm, agg):
     cols = []
     for o, W in zip(_offsets(lens), lens):
         a = A[:, :, o:o + W]
-        p = torch.softmax(LAMBDA_SOFTMAX * _first_norm(a, norm, 2), 1)
+        p = torch.softmax(lambda_softmax * _first_norm(a, norm, 2), 1)
         num = (p * a).sum(1)
         q = (p * (G @ p)).sum(1).clamp_min(0.0)
         s = num / (enorm[o:o + W] * q.sqrt()).clamp_min(1e-8)
@@ -169,7 +169,7 @@ def mirror_t2i(x, lens, norm, agg):
     return {'S': torch.stack(cols, 1)}
 
 
-def mirror_i2t(x, lens, norm, agg):
+def mirror_i2t(x, lens, norm, agg, lambda_softmax=LAMBDA_SOFTMAX):
     """scan_train_i2t.hip:3-9 (header), :52-59 (i2t_pair_forward) and scan_train_pair.h:63-134 (pair_forward with context = words,
     query = regions): A = V E^T, H_c = E_c E_c^T, ||v_r||; per pair u = first norm over the regions per word,
     p = softmax_w(lambda_s u), num_r = sum_w p a, q_r = p_r^T H_c p_r (clamped at 0, scan_train_pair.h:129),
@@ -183,7 +183,7 @@ def mirror_i2t(x, lens, norm, agg):
         Ec = E[o:o + W]
         H = Ec @ Ec.t()                                                # scan_train_i2t.hip:113-149
         a = A[:, :, o:o + W]
-        p = torch.softmax(LAMBDA_SOFTMAX * _first_norm(a, norm, 1), 2)
+        p = torch.softmax(lambda_softmax * _first_norm(a, norm, 1), 2)
         num = (p * a).sum(2)
         q = (p * (p @ H)).sum(2).clamp_min(0.0)
         s = num / (vnorm * q.sqrt()).clamp_min(1e-8)
