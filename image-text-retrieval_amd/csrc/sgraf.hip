@@ -1,7 +1,8 @@
 // SGRAF similarity: EncoderSimilarity.forward + VisualSA / TextSA / SCAN_attention / AttentionFiltration /
 // GraphReasoning (itr/modalmodule/Fusionmodule.py:373-664), eval mode (BatchNorm running statistics, no dropout).
 //
-// Structure (all heavy arithmetic on the fp32 matrix core), per block of 16 images (4 on the unfused path):
+// Structure (all heavy arithmetic on the fp32 matrix core), per block of 64 images (the default of the `image_block` argument, see
+// sgraf_ib below; 4 on the unfused path):
 //   1. SCAN kernel (scan_xattn.hip) in emit mode  -> attention weights P[i, word, 36] and 1/(||ctx||+eps)
 //      (SCAN_attention :632-664 is SCAN t2i with clipped_l2norm and smooth = 9)
 //   2+3. sim_loc = l2norm(W_loc (l2norm(P V) - E)^2 + b)   fused, (ctx - E)^2 stays on chip: sgraf_loc.hip (:425-427)

@@ -972,6 +972,8 @@ def _sgraf_weight_struct(weights, module_name, sgr_step):
         for f, name in _SAF_MAP.items():
             setattr(st, f, ptr(name))
     else:
+        if not 1 <= int(sgr_step) <= 8:      # (itr_sgraf_weights holds 8 steps: refused here as the library refuses it, not by an index error)
+            raise NotImplementedError("itr_sgraf_scores: sgr_step must be in [1, 8]")
         for k in range(sgr_step):
             pre = "SGR_module.sgr%d." % k
             st.sgr_q_w[k] = ptr(pre + "graph_query_w.weight"); st.sgr_q_b[k] = ptr(pre + "graph_query_w.bias")
