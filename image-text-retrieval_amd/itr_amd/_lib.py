@@ -81,6 +81,12 @@ SIGNATURES = {
     "itr_infonce_workspace_bytes": (sz, [i32]),
     "itr_infonce_fwd": (i32, [vp, vp, i32, i64, f32, vp, vp, vp, vp, vp]),
     "itr_infonce_bwd": (i32, [vp, vp, i32, i64, f32, vp, vp, vp, vp, i64, vp]),
+    "itr_xbm_workspace_bytes": (sz, [i32, i32]),
+    "itr_xbm_hinge_fwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp]),
+    "itr_xbm_hinge_bwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp]),
+    "itr_xbm_infonce_fwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "itr_xbm_infonce_bwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp]),
+    "itr_xbm_ring_write": (i32, [vp, vp, i64, i64, i64, i64, vp]),
     "itr_scan_plan_tiles": (i32, [vp, i64, i32, vp, vp, vp]),
     "itr_sgr_plan_node_groups": (i32, [vp, i64, i32, vp, vp, vp]),
     "itr_scan_workspace_bytes": (sz, [i64, i32, i64, i64, i64, i32]),

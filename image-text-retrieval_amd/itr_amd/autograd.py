@@ -368,7 +368,8 @@ class _Order(torch.autograd.Function):
         dS = dS.contiguous()
         d_im, d_s = torch.empty_like(im), torch.empty_like(s)
         _lib.check(lib.itr_order_bwd(_p(im), _p(s), _p(S), _p(dS), _p(d_im), _p(d_s), im.shape[0], s.shape[0], im.shape[1], _stream()))
-        return d_im, d_s
+        # one kernel writes both; an operand without a gradient (a cross-batch memory) hands none on to the tape
+        return (d_im if ctx.needs_input_grad[0] else None), (d_s if ctx.needs_input_grad[1] else None)
 
 
 def order_scores(im, s):

@@ -36,7 +36,11 @@ DEFAULTS = dict(
     # not keys of the reference: the ranking loss of training, 'hinge' (the reference's, with margin / max_violation) or 'infonce'
     # (softmax contrastive loss on scores / temperature, ops.infonce_loss).  Training switches like mask_same_image:
     # not in load_hyperparams, and model code reads them with .get so that configurations of old checkpoints still load
-    loss='hinge', temperature=0.05)
+    loss='hinge', temperature=0.05,
+    # not keys of the reference: memory_bank=M > 0 keeps the last M detached (image, caption) embeddings of the steps (VSE++, VSRN,
+    # SAEM) and ranks every query against batch u memory (itr_amd/membank.py, ops.xbm_hinge_loss / xbm_infonce_loss).
+    # The memory is pushed every step and used once Eiters > memory_start.  Training switches like `loss`; 0 is the step as it was
+    memory_bank=0, memory_start=0)
 
 NAMED = {
     'VSE_PP': dict(name="VSE++", data_name="f30k_precomp", vocab_type='pkl', val_step=10, img_dim=4096,

@@ -38,7 +38,10 @@ class base_module(nn.Module):
         self.optimizer = None
         self.params = None
         self.logger = None
-        self.train_im_div = None         # captions per image of the training set (train.py sets it); read by mask_same_image only
+        self.train_im_div = None         # captions per image of the training set (train.py sets it); read by mask_same_image and memory_bank
+        self.memory = None               # the cross-batch memory (membank.MemoryBank), made by the first step with memory_bank > 0
+        self._xbm_pending = None         # the step's rows, pushed once its backward has run
+        self._xbm_config()
 
     def calculate_params(self):
         self.params_num = sum(p.numel() for p in self.params)
@@ -67,6 +70,9 @@ class base_module(nn.Module):
         if self.sim_enc is not None:
             third = state_dict[2]
             self.sim_enc.load_state_dict(third.state_dict() if isinstance(third, nn.Module) else third)
+        self._xbm_pending = None
+        if self.memory is not None:      # stale embeddings belong to other weights
+            self.memory.reset()
 
     def train_start(self):
         self.img_enc.train()
@@ -123,6 +129,58 @@ class base_module(nn.Module):
             return ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'])
         return ops.hinge_loss(scores, self.config['margin'], self.config['max_violation'], groups=groups)
 
+    xbm_supported = False                # True in the families whose step forms scores = pair(img, cap) from two pooled matrices
+
+    def _xbm_config(self):
+        """memory_bank / memory_start are refused here, when the model is built, if they cannot mean anything."""
+        cfg = self.config
+        for key in ('memory_bank', 'memory_start'):
+            v = cfg.get(key, 0)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (key, v))
+        M = cfg.get('memory_bank', 0)
+        if M > 0 and not self.xbm_supported:
+            raise ValueError("memory_bank=%d: %s has no cross-batch memory (VSE++, VSRN and SAEM have one: their step scores two pooled "
+                             "embedding matrices; word-level and multi-view memories are not built)" % (M, type(self).__name__))
+        if 0 < M < cfg.get('batch_size', 0):
+            raise ValueError("memory_bank=%d is smaller than batch_size=%d: a step's rows would not fit the memory" % (M, cfg['batch_size']))
+
+    def _hinge_memory(self, img, cap, scores, ids, pair_fn, groups=None, comm=None):
+        """The retrieval loss of a step of the pooled families, `scores` = pair_fn(img, cap).  config['memory_bank'] = 0 (the
+        default), or a memory not yet in use: self._hinge(scores, groups), the very call the step made before.  Otherwise every query
+        also ranks against the memory: R = pair_fn(img, memory captions) and C = pair_fn(memory images, cap) go on the tape (the memory
+        carries no gradient) and config['loss'] picks ops.xbm_hinge_loss or ops.xbm_infonce_loss.  The step's (img, cap) are pushed
+        every step -- by _step, after the backward, because the memory's tables are operands saved on the tape."""
+        M = self.config.get('memory_bank', 0)
+        if not M:
+            return self._hinge(scores, groups)
+        if comm is not None and comm.on:
+            raise ValueError("memory_bank=%d under data parallelism (%d ranks): every rank would keep its own memory of the gathered "
+                             "embeddings; a memory is built for one process only" % (M, comm.world))
+        if not self.train_im_div:
+            raise ValueError("memory_bank=%d needs model.train_im_div, the captions per image of the training set "
+                             "(train.py sets it from the dataset's im_div; 5 for the precomp splits)" % M)
+        from ..membank import MemoryBank
+        own = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1) // int(self.train_im_div)
+        if scores.shape[0] > M:
+            raise ValueError("memory_bank=%d is smaller than the batch of %d" % (M, scores.shape[0]))
+        if self.memory is None or self.memory.capacity != M:
+            self.memory = MemoryBank(M, scores.device)
+        if self.Eiters > self.config.get('memory_start', 0) and len(self.memory) > 0:
+            bank_img, bank_cap, bank_groups = self.memory.view()
+            R = pair_fn(img, bank_cap)
+            C = pair_fn(bank_img, cap)
+            mask_batch = bool(self.config.get('mask_same_image', False))
+            if Objectives.retrieval_loss_kind(self.config) == 'infonce':
+                loss = ops.xbm_infonce_loss(scores, R, C, own, bank_groups, self.config.get('temperature', 0.05), mask_batch=mask_batch)
+            else:
+                loss = ops.xbm_hinge_loss(scores, R, C, own, bank_groups, self.config['margin'], self.config['max_violation'],
+                                          mask_batch=mask_batch)
+        else:
+            loss = self._hinge(scores, groups)
+        self._xbm_pending = (img.detach(), cap.detach(), own)
+        return loss
+
     def _hinge_groups(self, ids, comm):
         """config['mask_same_image'] off (the default, and every configuration read from an old checkpoint): None.  On: the image of
         every pair, ids // train_im_div (host array), in the ROW ORDER OF THE SCORE MATRIX the step hands to the hinge -- the batch
@@ -160,6 +218,9 @@ class base_module(nn.Module):
         whole batch when `loss` holds only this rank's part of a term (data parallel)."""
         self._log('Loss', loss.detach() if logged is None else logged, batch_size)      # a device scalar like the reference's loss.data: no host sync here
         loss.backward()
+        if self._xbm_pending is not None:
+            pending, self._xbm_pending = self._xbm_pending, None
+            self.memory.push(*pending)
         self.optimizer.step(max_norm=self.grad_clip if self.grad_clip > 0 else 0.0)
 
     @staticmethod
@@ -170,6 +231,8 @@ class base_module(nn.Module):
 class VSE_PP(base_module):
     """VSE++ (Models.py:63-145) with the build decisions of SURVEY Q3 for *_precomp data: mean-pooled regions
     -> fc -> l2norm; text = last valid GRU state -> l2norm; honours bi_gru."""
+
+    xbm_supported = True
 
     def __init__(self, config):
         super().__init__(config)
@@ -214,7 +277,7 @@ class VSE_PP(base_module):
                 scores = ag.dp_gather_rows(pair_scores(img, cap), comm, rows, reduce=False)
             else:
                 scores = pair_scores(img, cap)
-            loss = self._hinge(scores, groups)
+            loss = self._hinge_memory(img, cap, scores, ids, pair_scores, groups, comm)
             self._step(loss, scores.size(0))
 
     def forward_loss(self, img_emb, cap_emb):
@@ -284,6 +347,8 @@ class VSRN(base_module):
     tower, cosine similarity, plus the training-only captioning branch (EncoderRNN / attention DecoderRNN over the GCN region
     features, LanguageModelCriterion).  The reference's checkpoints hold [img_enc, txt_enc] only (Models.py:37-45: the captioning
     model is never saved) -- the same here."""
+
+    xbm_supported = True
 
     def __init__(self, config, use_txt_emb=True):
         super().__init__(config)
@@ -379,8 +444,9 @@ class VSRN(base_module):
             if comm.on:
                 img = ag.dp_gather_rows(img, comm, rows, reduce=False)
                 cap = ag.dp_gather_rows(cap, comm, rows, reduce=False)
-            scores = (ag.order_scores if self.config['measure'] == 'order' else ag.cosine_scores)(img, cap)
-            retrieval_loss = self._hinge(scores, groups)
+            pair_scores = ag.order_scores if self.config['measure'] == 'order' else ag.cosine_scores
+            scores = pair_scores(img, cap)
+            retrieval_loss = self._hinge_memory(img, cap, scores, ids, pair_scores, groups, comm)
             caption_loss = self.caption_model.caption_loss_train(gcn_emb, captions, self._dev(captions_mask), self._seeds,
                                                                  self.caption_model.training, batch_total=n_batch)
             caption_total = caption_loss.detach()
@@ -463,6 +529,8 @@ class SGRAF(base_module):
 class SAEM(base_module):
     """SAEM (Models.py:369-464): BERT text tower + transformer image tower, cosine via pdist_cos."""
 
+    xbm_supported = True
+
     def __init__(self, config):
         super().__init__(config)
         self.img_enc = ImgEncoder.TransformerMapping(config)
@@ -538,8 +606,9 @@ class SAEM(base_module):
                 cap = ag.dp_gather_rows(cap, comm, rows, reduce=False)
                 lengths, ids = lengths_all, ids_all
             # criterion = hinge on pdist_cos (Objectives.py:310-323: rows renormalised, no eps), on the tape
-            scores = ag.cosine_scores(ag.l2norm_rows(img, eps=0.0), ag.l2norm_rows(cap, eps=0.0))
-            loss1 = self._hinge(scores, groups)
+            img_n, cap_n = ag.l2norm_rows(img, eps=0.0), ag.l2norm_rows(cap, eps=0.0)
+            scores = ag.cosine_scores(img_n, cap_n)
+            loss1 = self._hinge_memory(img_n, cap_n, scores, ids, ag.cosine_scores, groups, comm)
             alpha = 0 if epoch > 20 else 0.5 * (0.1 ** (epoch // 5))
             loss2 = self.criterion_2(img, cap, lengths, ids)
             l2_reg = torch.zeros((), device=img.device)

@@ -507,6 +507,159 @@ def infonce_loss(scores, temperature=0.05, groups=None):
     return _InfoNCEFn.apply(scores, temperature, groups)
 
 
+# ---- cross-batch memory: both losses on batch u memory (csrc/xbm_loss.hip)
+def _xbm_operands(who, S, R, C, groups, bank_groups):
+    """Checked (S [B, B], R [B, n], C [n, B], groups int32 [B], bank_groups int32 [n]) on S's device."""
+    S, R, C = _dev(S, name="S"), _dev(R, name="R"), _dev(C, name="C")
+    if S.dim() != 2 or S.shape[0] != S.shape[1]:
+        raise ValueError("%s needs a square score matrix, got %s" % (who, tuple(S.shape)))
+    B = S.shape[0]
+    if B < 1:
+        raise ValueError("%s needs at least one pair, got S %s" % (who, tuple(S.shape)))
+    if R.dim() != 2 or C.dim() != 2 or R.shape[0] != B or C.shape[1] != B or C.shape[0] != R.shape[1]:
+        raise ValueError("%s needs R [%d, n] and C [n, %d], got R %s and C %s" % (who, B, B, tuple(R.shape), tuple(C.shape)))
+    if R.device != S.device or C.device != S.device:
+        raise ValueError("%s: S, R and C must lie on one device, got %s, %s, %s" % (who, S.device, R.device, C.device))
+    n = R.shape[1]
+    if B * (B + 2 * n) >= 2 ** 31:
+        raise ValueError("%s: B (B + 2 n) must stay below 2^31, got B=%d n=%d" % (who, B, n))
+    if groups is None or bank_groups is None:
+        raise ValueError("%s needs the image of every pair (groups) and of every memory slot (bank_groups)" % who)
+    return S, R, C, _hinge_groups(groups, B, S.device), _hinge_groups(bank_groups, n, S.device)
+
+
+def xbm_hinge_fwd(S, R, C, groups, bank_groups, margin, max_violation, mask_batch=False):
+    """-> (loss[1], row_arg[B], col_arg[B]) of the hinge on batch u memory (itr_xbm_hinge_fwd).  Max form: candidate indices in
+    [0, B + n), < B in-batch, else memory slot arg - B.  Sum form: the violator counts of every row / column."""
+    lib = _lib.load()
+    S, R, C, groups, bank_groups = _xbm_operands("XBM hinge loss", S, R, C, groups, bank_groups)
+    B, n = R.shape
+    loss = torch.empty(1, device=S.device, dtype=torch.float32)
+    row_arg = torch.empty(B, device=S.device, dtype=torch.int32)
+    col_arg = torch.empty(B, device=S.device, dtype=torch.int32)
+    ws = torch.empty(max(1, int(lib.itr_xbm_workspace_bytes(B, n))), device=S.device, dtype=torch.uint8)
+    _lib.check(lib.itr_xbm_hinge_fwd(_p(S), B, _p(R), n, _p(C), B, _p(groups), _p(bank_groups), B, n, int(bool(mask_batch)),
+                                     float(margin), int(bool(max_violation)), _p(loss), _p(row_arg), _p(col_arg), _p(ws), _stream()))
+    return loss, row_arg, col_arg
+
+
+def xbm_hinge_bwd(S, R, C, groups, bank_groups, margin, max_violation, row_arg, col_arg, grad_loss, mask_batch=False):
+    """-> (dS, dR, dC) of xbm_hinge_fwd from its saved arg vectors (itr_xbm_hinge_bwd); bit-zero at dropped entries."""
+    lib = _lib.load()
+    S, R, C, groups, bank_groups = _xbm_operands("XBM hinge loss", S, R, C, groups, bank_groups)
+    B, n = R.shape
+    row_arg, col_arg = _dev(row_arg, torch.int32, "row_arg"), _dev(col_arg, torch.int32, "col_arg")
+    if row_arg.shape != (B,) or col_arg.shape != (B,):
+        raise ValueError("XBM hinge loss: row_arg and col_arg must have length %d" % B)
+    g = _dev(grad_loss.reshape(1), name="grad_loss")
+    dS, dR, dC = torch.empty_like(S), torch.empty_like(R), torch.empty_like(C)
+    _lib.check(lib.itr_xbm_hinge_bwd(_p(S), B, _p(R), n, _p(C), B, _p(groups), _p(bank_groups), B, n, int(bool(mask_batch)),
+                                     float(margin), int(bool(max_violation)), _p(row_arg), _p(col_arg), _p(g), _p(dS), B, _p(dR), n,
+                                     _p(dC), B, _stream()))
+    return dS, dR, dC
+
+
+def xbm_infonce_fwd(S, R, C, groups, bank_groups, temperature=0.05, mask_batch=False):
+    """-> (loss[1], row_lse[B], col_lse[B]) of the InfoNCE loss on batch u memory (itr_xbm_infonce_fwd)."""
+    lib = _lib.load()
+    S, R, C, groups, bank_groups = _xbm_operands("XBM InfoNCE loss", S, R, C, groups, bank_groups)
+    scale = _infonce_scale(temperature)
+    B, n = R.shape
+    loss = torch.empty(1, device=S.device, dtype=torch.float32)
+    row_lse = torch.empty(B, device=S.device, dtype=torch.float32)
+    col_lse = torch.empty(B, device=S.device, dtype=torch.float32)
+    ws = torch.empty(max(1, int(lib.itr_xbm_workspace_bytes(B, n))), device=S.device, dtype=torch.uint8)
+    _lib.check(lib.itr_xbm_infonce_fwd(_p(S), B, _p(R), n, _p(C), B, _p(groups), _p(bank_groups), B, n, int(bool(mask_batch)), scale,
+                                       _p(loss), _p(row_lse), _p(col_lse), _p(ws), _stream()))
+    return loss, row_lse, col_lse
+
+
+def xbm_infonce_bwd(S, R, C, groups, bank_groups, temperature, row_lse, col_lse, grad_loss, mask_batch=False):
+    """-> (dS, dR, dC) of xbm_infonce_fwd from its saved log-sum-exps (itr_xbm_infonce_bwd); bit-zero at dropped entries."""
+    lib = _lib.load()
+    S, R, C, groups, bank_groups = _xbm_operands("XBM InfoNCE loss", S, R, C, groups, bank_groups)
+    scale = _infonce_scale(temperature)
+    B, n = R.shape
+    row_lse, col_lse = _dev(row_lse, name="row_lse"), _dev(col_lse, name="col_lse")
+    if row_lse.shape != (B,) or col_lse.shape != (B,):
+        raise ValueError("XBM InfoNCE loss: row_lse and col_lse must have length %d" % B)
+    g = _dev(grad_loss.reshape(1), name="grad_loss")
+    dS, dR, dC = torch.empty_like(S), torch.empty_like(R), torch.empty_like(C)
+    _lib.check(lib.itr_xbm_infonce_bwd(_p(S), B, _p(R), n, _p(C), B, _p(groups), _p(bank_groups), B, n, int(bool(mask_batch)), scale,
+                                       _p(row_lse), _p(col_lse), _p(g), _p(dS), B, _p(dR), n, _p(dC), B, _stream()))
+    return dS, dR, dC
+
+
+class _XbmHingeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, R, C, groups, bank_groups, margin, max_violation, mask_batch):
+        S, R, C = S.contiguous(), R.contiguous(), C.contiguous()
+        loss, ra, ca = xbm_hinge_fwd(S, R, C, groups, bank_groups, margin, max_violation, mask_batch)
+        ctx.save_for_backward(S, R, C, groups, bank_groups, ra, ca)
+        ctx.margin, ctx.mv, ctx.mask_batch = margin, max_violation, mask_batch
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad):
+        S, R, C, groups, bank_groups, ra, ca = ctx.saved_tensors
+        dS, dR, dC = xbm_hinge_bwd(S, R, C, groups, bank_groups, ctx.margin, ctx.mv, ra, ca, grad.contiguous(), ctx.mask_batch)
+        return (dS, dR, dC) + (None,) * 5
+
+
+class _XbmInfoNCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, R, C, groups, bank_groups, temperature, mask_batch):
+        S, R, C = S.contiguous(), R.contiguous(), C.contiguous()
+        loss, row_lse, col_lse = xbm_infonce_fwd(S, R, C, groups, bank_groups, temperature, mask_batch)
+        ctx.save_for_backward(S, R, C, groups, bank_groups, row_lse, col_lse)
+        ctx.temperature, ctx.mask_batch = temperature, mask_batch
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad):
+        S, R, C, groups, bank_groups, row_lse, col_lse = ctx.saved_tensors
+        dS, dR, dC = xbm_infonce_bwd(S, R, C, groups, bank_groups, ctx.temperature, row_lse, col_lse, grad.contiguous(), ctx.mask_batch)
+        return (dS, dR, dC) + (None,) * 4
+
+
+def xbm_hinge_loss(S, R, C, groups, bank_groups, margin, max_violation, mask_batch=False):
+    """Differentiable (w.r.t. S, R and C) bidirectional hinge on batch u memory, HIP forward and backward.  S [B, B] is the step's
+    matrix, R [B, n] scores the images against the memory's captions, C [n, B] the memory's images against the captions.  `groups`
+    [B] / `bank_groups` [n] (as in hinge_loss) name the image of every pair / memory slot: a memory entry of the query's own image
+    is never a negative; inside the batch the same rule holds with mask_batch=True.  With an empty memory (n = 0) this is hinge_loss
+    on S, bit for bit."""
+    S, R, C, groups, bank_groups = _xbm_operands("XBM hinge loss", S, R, C, groups, bank_groups)
+    if R.shape[1] == 0:
+        return hinge_loss(S, margin, max_violation, groups=groups if mask_batch else None)
+    return _XbmHingeFn.apply(S, R, C, groups, bank_groups, margin, bool(max_violation), bool(mask_batch))
+
+
+def xbm_infonce_loss(S, R, C, groups, bank_groups, temperature, mask_batch=False):
+    """Differentiable (w.r.t. S, R and C) InfoNCE loss on batch u memory: every row's and every column's softmax also ranges over the
+    memory's kept entries.  Operands and the two group vectors as in xbm_hinge_loss; n = 0 is infonce_loss on S, bit for bit."""
+    S, R, C, groups, bank_groups = _xbm_operands("XBM InfoNCE loss", S, R, C, groups, bank_groups)
+    _infonce_scale(temperature)
+    if R.shape[1] == 0:
+        return infonce_loss(S, temperature, groups=groups if mask_batch else None)
+    return _XbmInfoNCEFn.apply(S, R, C, groups, bank_groups, temperature, bool(mask_batch))
+
+
+def xbm_ring_write(src, table, head):
+    """table[(head + r) % M] = src[r] for every row of `src` (itr_xbm_ring_write): one launch, across the wrap.  Both are contiguous
+    device tensors of one 32-bit dtype with equal row shapes."""
+    lib = _lib.load()
+    if not (torch.is_tensor(src) and torch.is_tensor(table) and src.is_cuda and table.is_cuda):
+        raise RuntimeError("xbm_ring_write: the itr_amd ops only run on the GPU (no CPU fallback)")
+    if src.dtype != table.dtype or src.dtype.itemsize != 4:
+        raise TypeError("xbm_ring_write: src and table must share one 32-bit dtype, got %s and %s" % (src.dtype, table.dtype))
+    if src.dim() < 1 or src.shape[1:] != table.shape[1:] or src.shape[0] > table.shape[0] or not table.is_contiguous():
+        raise ValueError("xbm_ring_write: src %s does not fit rows of table %s" % (tuple(src.shape), tuple(table.shape)))
+    src = src.contiguous()
+    M = table.shape[0]
+    width = int(np.prod(table.shape[1:])) if table.dim() > 1 else 1
+    _lib.check(lib.itr_xbm_ring_write(_p(src), _p(table), M, width, int(head), src.shape[0], _stream()))
+
+
 # ------------------------------------------------------------------------------------------
 class ScanPlan:
     """Column-tile plan of a caption set for the SCAN kernel (host-side, cheap, reusable).

@@ -225,6 +225,56 @@ int itr_infonce_fwd(const float *S, const int32_t *group /* or NULL */, int B, i
 int itr_infonce_bwd(const float *S, const int32_t *group /* or NULL */, int B, int64_t ldS, float scale, const float *row_lse,
                     const float *col_lse, const float *grad_loss, float *dS, int64_t lddS, itr_stream_t stream);
 
+/* ---- Cross-batch memory (XBM): the two losses above on batch u memory.  S [B, B] is the step's matrix (image i vs caption j); R [B, n]
+ * scores image i against memory caption k and C [n, B] memory image k against caption j, the memory being n detached (image, caption)
+ * embeddings of earlier steps.  Row i's candidates are S[i, :] then R[i, :], column j's are S[:, j] then C[:, j]; a candidate index
+ * t in [0, B + n) is in-batch for t < B and memory slot t - B otherwise.  The entries replace no reference line.
+ *   group[B], bank_group[n] (int32, device; any values; never NULL -- bank_group may be NULL when n == 0).  Kept sets:
+ *     S (i, j), i != j: dropped iff mask_batch && group[i] == group[j]   (the rule of itr_hinge_groups_*; the diagonal is the positive)
+ *     R (i, k):         dropped iff group[i] == bank_group[k]            (always: a stored caption of the query's own image)
+ *     C (k, j):         dropped iff bank_group[k] == group[j]
+ *   A dropped entry is skipped, never fed into the arithmetic, and its gradient is bit-zero.
+ * Hinge: cost = max(0, (margin + s) - d) in fp32, d = S[q,q]; the diagonal and dropped entries cost 0.
+ *     sum form  loss = all row-side costs over S and R + all column-side costs over S and C
+ *     max form  loss = sum_i max(row i's candidates) + sum_j max(column j's candidates)
+ *   row_arg[B], col_arg[B] (required in both forms): max form -- the candidate index of the largest cost; the larger cost wins, on
+ *   equal costs the earlier candidate (in-batch ascending, then slots ascending), chosen among kept candidates and the diagonal only.
+ *   Sum form -- the number of violators of the row / column (the diagonal's gradient is -g (row_arg[i] + col_arg[i])).
+ *   bwd checks range and mask of the saved args again; max form: at most one nonzero per row of dR and per column of dC.
+ * InfoNCE: scale = float32(1 / temperature), z = scale * s (one fp32 product).
+ *     row_lse[i] = log( sum_{j kept} exp zS[i,j] + sum_{k kept} exp zR[i,k] )
+ *     col_lse[j] = log( sum_{i kept} exp zS[i,j] + sum_{k kept} exp zC[k,j] )
+ *     loss = ( sum_i (row_lse[i] - zS[i,i]) + sum_j (col_lse[j] - zS[j,j]) ) / (2 B)
+ *     dS[i,j] = g scale / (2 B) ( exp(zS[i,j] - row_lse[i]) + exp(zS[i,j] - col_lse[j]) - 2 [i == j] ),
+ *     dR[i,k] = g scale / (2 B) exp(zR[i,k] - row_lse[i]),   dC[k,j] = g scale / (2 B) exp(zC[k,j] - col_lse[j])   on kept, 0 elsewhere
+ *   Every log-sum-exp is a running (max, sum) pair; the empty set is the pair with sum 0.
+ * fwd needs itr_xbm_workspace_bytes(B, n) bytes of scratch.  Rows are read by one wave each; for the columns a workgroup owns 64
+ * adjacent columns and one slice of the B + n candidate rows, read in whole 256-byte row segments, and a finishing workgroup merges
+ * the slices in slice order and sums the 2B terms in float64.  Deterministic: no float atomics, two runs give the same bits.
+ * bwd writes every entry of dS [B,B], dR [B,n] and dC [n,B] once, zeros included; g = grad_loss[0] (device scalar).
+ * Host checks before anything touches the device (ITR_ERR_BADARG, "<entry>: ..."): null pointers, B < 1, n < 0, ldS < B, ldR < n,
+ * ldC < B (and lddS / lddR / lddC alike), B (B + 2 n) >= 2^31, scale not finite or <= 0.
+ * itr_xbm_ring_write: table[(head + r) % capacity, :] = src[r, :] for r < count, rows of `width` 32-bit words -- one launch writes a
+ * push of the memory's FIFO across the wrap (0 <= head < capacity, count <= capacity).
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+size_t itr_xbm_workspace_bytes(int B, int n);
+int itr_xbm_hinge_fwd(const float *S, int64_t ldS, const float *R, int64_t ldR, const float *C, int64_t ldC, const int32_t *group,
+                      const int32_t *bank_group, int B, int n, int mask_batch, float margin, int max_violation, float *loss,
+                      int32_t *row_arg, int32_t *col_arg, void *workspace, itr_stream_t stream);
+int itr_xbm_hinge_bwd(const float *S, int64_t ldS, const float *R, int64_t ldR, const float *C, int64_t ldC, const int32_t *group,
+                      const int32_t *bank_group, int B, int n, int mask_batch, float margin, int max_violation,
+                      const int32_t *row_arg, const int32_t *col_arg, const float *grad_loss, float *dS, int64_t lddS, float *dR,
+                      int64_t lddR, float *dC, int64_t lddC, itr_stream_t stream);
+int itr_xbm_infonce_fwd(const float *S, int64_t ldS, const float *R, int64_t ldR, const float *C, int64_t ldC, const int32_t *group,
+                        const int32_t *bank_group, int B, int n, int mask_batch, float scale, float *loss, float *row_lse,
+                        float *col_lse, void *workspace, itr_stream_t stream);
+int itr_xbm_infonce_bwd(const float *S, int64_t ldS, const float *R, int64_t ldR, const float *C, int64_t ldC, const int32_t *group,
+                        const int32_t *bank_group, int B, int n, int mask_batch, float scale, const float *row_lse,
+                        const float *col_lse, const float *grad_loss, float *dS, int64_t lddS, float *dR, int64_t lddR, float *dC,
+                        int64_t lddC, itr_stream_t stream);
+int itr_xbm_ring_write(const void *src, void *table, int64_t capacity, int64_t width, int64_t head, int64_t count,
+                       itr_stream_t stream);
+
 /* ---- a6: xattn_score_t2i / xattn_score_i2t (Objectives.py:329-476) ---------------------
  * img [Ni,R,D]; words [n_rows,D] with caption c owning rows cap_off[c] .. cap_off[c]+len[c]-1
  * (padded (Nc,L,D) input: cap_off[c] = c*L).  S[i,c] written with row stride ldS.

@@ -115,13 +115,13 @@ def oracle_cpu_step(model_name, batch, cfg, model=None):
     return time.perf_counter() - t0
 
 
-def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=None, mask_same_image=False, cross_attn='t2i', loss='hinge'):
+def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=None, mask_same_image=False, cross_attn='t2i', loss='hinge', memory_bank=0):
     from itr_amd import config as C
     from itr_amd.modalmodule import get_model
     from itr_amd.metricmodule.evaluation import LogCollector
     dev = dev or torch.device("cuda", 0)
     cfg = C.build_config(['with', model_name, 'data_name=coco_precomp', 'bi_gru=True', 'max_violation=True',
-                          'mask_same_image=%s' % bool(mask_same_image), 'loss=' + loss] + (['module_name=' + module] if model_name == 'SGRAF' else [])
+                          'mask_same_image=%s' % bool(mask_same_image), 'loss=' + loss, 'memory_bank=%d' % memory_bank] + (['module_name=' + module] if model_name == 'SGRAF' else [])
                          + (['cross_attn=' + cross_attn] if model_name == 'SCAN' else []))
     cfg['vocab_size'] = V_COCO
     cfg['img_dim'] = 2048        # precomp region features
@@ -149,7 +149,7 @@ def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=N
         marks['bwd_end'] = ev(); marks['bwd_end'].record()
         return orig_opt(*a, **k)
     model._step, model.optimizer.step = _step, _opt
-    for i in range(warmup):
+    for i in range(warmup + -(-memory_bank // batch)):          # the timed steps see a full memory
         model.train_emb(batches[i % 4])
     torch.cuda.synchronize()
     split = np.zeros(3)
@@ -171,7 +171,7 @@ def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=N
     meter = model.logger.meters['Loss' if 'Loss' in model.logger.meters else 'Loss1']
     row = {"family": name, "batch": batch, "words": int(sum(lens)), "steps": steps, "warmup": warmup, "ms_per_step": round(dt * 1e3, 3),
            "pairs_per_s": round(batch * batch / dt, 1), "forward_ms": round(float(split[0]), 3), "backward_ms": round(float(split[1]), 3),
-           "optimizer_ms": round(float(split[2]), 3), "loss": round(float(meter.val), 4), "loss_kind": loss,
+           "optimizer_ms": round(float(split[2]), 3), "loss": round(float(meter.val), 4), "loss_kind": loss, "memory_bank": memory_bank,
            "reference": "Models.py train_emb (:115-145, :205-225, :444-464, :518-546, :606-645); utils.py:80-102 times each batch"}
     if fm is not None:
         row["flop_model"] = fm
@@ -219,6 +219,7 @@ def main():
     ap.add_argument("--cpu", action="store_true", help="time the oracle's training step on the host cores beside VSE++ / SCAN")
     ap.add_argument("--budget", type=float, default=1e9, help="--all: seconds after which no further family is started")
     ap.add_argument("--mask-same-image", action="store_true", help="time the step with mask_same_image=True (the hinge with the group mask)")
+    ap.add_argument("--memory-bank", type=int, default=0, help="time the step with a cross-batch memory of this many pairs, filled before the timed steps (config key `memory_bank`; VSE_PP, VSRN, SAEM)")
     ap.add_argument("--loss", default="hinge", choices=["hinge", "infonce"], help="the ranking loss of the step (config key `loss`; infonce at the default temperature)")
     ap.add_argument("--cross-attn", default="t2i", choices=["t2i", "i2t"], help="SCAN: the direction of the cross attention")
     a = ap.parse_args()
@@ -231,7 +232,7 @@ def main():
             rows[name] = {"error": "not started: the time budget of the run was spent"}
             continue
         try:
-            r = run(model_name, module, a.batch or batch, a.steps, a.warmup, cpu=a.cpu, mask_same_image=a.mask_same_image, cross_attn=a.cross_attn, loss=a.loss)
+            r = run(model_name, module, a.batch or batch, a.steps, a.warmup, cpu=a.cpu, mask_same_image=a.mask_same_image, cross_attn=a.cross_attn, loss=a.loss, memory_bank=a.memory_bank)
         except Exception as e:      # noqa: BLE001  (one family must not take the others' rows with it)
             r = {"family": name, "error": "%s: %s" % (type(e).__name__, e)}
         rows[name] = r
