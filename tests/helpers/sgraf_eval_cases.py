@@ -234,9 +234,11 @@ def _lin(x, w, p):
     return x @ w[p + '.weight'].t() + w[p + '.bias']
 
 
-def mirror(w, img, words, lens, mod, steps, dup_last=False, glo_wrap=False, tail_img=False, bn_shift=False, stats=None):
+def mirror(w, img, words, lens, mod, steps, dup_last=False, glo_wrap=False, tail_img=False, bn_shift=False, stats=None, gram=None, tail=None):
     """The library's algebra (sgraf.hip:1-12, :646-651; sgraf_loc.hip; sgr_fused.hip; scan_xattn.hip in emit mode).  The keyword
-    arguments are the mirror's defects (module docstring: k, g, t, n); stats: a dict that receives the sharpness figures."""
+    arguments are the mirror's defects (module docstring: k, g, t, n); stats: a dict that receives the sharpness figures.
+    For the candidate-list table (sgraf_pairs_cases.py): gram(G) changes the images' Gram matrices; tail(c, x, attn) -> the logits of
+    caption c from its node rows x [Ni, n + 1, S] and SCAN attention weights attn [Ni, n, 36] stands in for the SAF / SGR stage."""
     Ni, R, D = img.shape
     one = torch.ones((), dtype=img.dtype)
     # VisualSA (sgraf.hip:399-420): BatchNorm1d(36) by region row (bn_tanh_kernel, slabs of 65 520 rows), BatchNorm1d(D) by column
@@ -258,6 +260,8 @@ def mirror(w, img, words, lens, mod, steps, dup_last=False, glo_wrap=False, tail
         img_glo = img_glo.clone()
         img_glo[-1] = img_glo[0]
     G = img @ img.transpose(1, 2)                                          # the images' Gram matrices (scan_xattn.hip gram_mfma_kernel)
+    if gram is not None:
+        G = gram(G)
     # TextSA per caption (sgraf.hip:421-427)
     cap_glo = []
     for o, n in zip(_offsets(lens), lens):
@@ -295,7 +299,9 @@ def mirror(w, img, words, lens, mod, steps, dup_last=False, glo_wrap=False, tail
         xg = _lin((img_glo - cap_glo[c][None]) ** 2, w, 'sim_tranglo_w')   # the one-hot context is img_glo itself
         xg = xg / ((xg * xg).sum(1, keepdim=True).sqrt() + 1e-8)
         x = torch.cat([xg[:, None, :], xl], 1)                             # (Ni, n + 1, S)
-        if mod == 'SAF':                                                   # sgraf.hip:145-228 (saf_pair_kernel)
+        if tail is not None:
+            sc = tail(c, x, (e * rden[:, None, :]).transpose(1, 2))
+        elif mod == 'SAF':                                                 # sgraf.hip:145-228 (saf_pair_kernel)
             s = x @ w['SAF_module.attn_sim_w.weight'][0] + w['SAF_module.attn_sim_w.bias'][0]
             at = torch.sigmoid((s - w[pb + '.running_mean'][0]) * bscale + w[pb + '.bias'][0])
             if dup_last:
@@ -317,7 +323,7 @@ def mirror(w, img, words, lens, mod, steps, dup_last=False, glo_wrap=False, tail
                 x = torch.relu(_lin(edge @ keys, w, pre + 'sim_graph_w'))  # last: node 0 only, one projection (sgraf.hip:470)
             sc = (x[:, 0] * w['sim_eval_w.weight'][0]).sum(1) + w['sim_eval_w.bias'][0]
         cols.append(torch.sigmoid(sc))
-    if stats is not None:
+    if stats is not None and sharp:                  # (with `tail` nothing is collected)
         stats['sharp'] = float(torch.cat(sharp).mean())
     return torch.stack(cols, 1)
 
