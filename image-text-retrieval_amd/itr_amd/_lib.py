@@ -126,6 +126,11 @@ SIGNATURES = {
     "itr_topk_f64": (i32, [vp, i64, i64, i64, i32, vp, vp, vp, vp, vp]),
     "itr_topk_fold_workspace_bytes": (sz, [i64, i64, i32]),
     "itr_topk_fold_cols": (i32, [vp, i64, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
+    "itr_hub_lse_workspace_bytes": (sz, [i64, i64]),
+    "itr_hub_lse_fold": (i32, [vp, i32, i64, i64, i64, C.c_double, vp, vp, vp, sz, vp]),
+    "itr_hub_lse_finish": (i32, [vp, i64, C.c_double, vp, vp]),
+    "itr_hub_list_mean": (i32, [vp, i32, i64, i64, i32, vp, vp]),
+    "itr_hub_adjust": (i32, [vp, i32, i64, i64, i64, vp, vp, vp, i64, vp]),
     "itr_scan_pairs_workspace_bytes": (sz, [i64, i32, i64, i64, i32]),
     "itr_scan_pairs_prepare": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, sz, vp]),
     "itr_sgraf_pairs_state_bytes": (sz, [i64, i64, i64, i32, i32, i32, i32]),

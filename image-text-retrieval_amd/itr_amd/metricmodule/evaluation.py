@@ -307,6 +307,203 @@ def _save_gt(save_dir, data_name, tag, res, gt):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Hubness correction before ranking: S'[i, j] = S[i, j] - a[i] - b[j].  a is constant along a row, so the i2t order
+# is corrected by b alone (it penalises hub captions), and b along a column, so the t2i order by a alone: ONE adjusted matrix serves
+# both directions and every consumer of a similarity matrix (cal_recall, topk, gt_metrics, rerank) works on it unchanged.
+HUBNESS_METHODS = ('csls', 'invsoftmax')
+
+
+def _check_hubness(who, method, k, beta):
+    if method not in HUBNESS_METHODS:
+        raise ValueError("%s: hubness must be one of %s, got %r" % (who, HUBNESS_METHODS, method))
+    if method == 'csls' and (int(k) != k or k < 1):
+        raise ValueError("%s: hub_k = %r must be an integer >= 1" % (who, k))
+    if method == 'invsoftmax' and not (float(beta) > 0.0 and np.isfinite(float(beta))):
+        raise ValueError("%s: hub_beta = %r must be finite and positive" % (who, beta))
+
+
+def hubness_vectors(sims, method, k=10, beta=20.0):
+    """The correction vectors of the query bank `self`: the statistics of the evaluated matrix sims [Ni, Nc] itself (transductive).
+    method 'invsoftmax' (Smith et al. 2017): a[i] = (1 / beta) log sum_q exp(beta sims[i, q]), b[j] the same down column j -- ONE
+    `ops.hub_lse_fold` over the matrix.  method 'csls' (Conneau et al. 2018): a[i] = 0.5 * mean of the k largest of row i, b[j] of
+    column j, the k largest in the ranker's order (`ops.topk_lists` + `ops.topk_merge_cols`, then `ops.hub_list_mean`).  float32
+    input is reduced as float32 widened to double, anything else in float64 (as `_ranks`).  -> (a [Ni], b [Nc]) float64 numpy."""
+    _check_hubness("hubness_vectors", method, k, beta)
+    S = _device_matrix(sims)
+    if method == 'invsoftmax':
+        a, state = ops.hub_lse_fold(S, beta)
+        b = ops.hub_lse_cols(state, beta)
+    else:
+        k = int(k)
+        if k > min(S.shape):
+            raise ValueError("hubness_vectors: k = %d is larger than a side of the %d x %d matrix" % (k, S.shape[0], S.shape[1]))
+        _, r_val, part = ops.topk_lists(S, k)
+        _, c_val = ops.topk_merge_cols([part], k)
+        a, b = ops.hub_list_mean(r_val, k), ops.hub_list_mean(c_val, k)
+    return a.cpu().numpy(), b.cpu().numpy()
+
+
+def _hub_block_scorer(members, n_cols, shard_sizes):
+    """-> f(i0, i1): the device matrix [i1 - i0, n_cols] of image rows i0 .. i1 - 1 against ALL caption columns, scored with every
+    member's own cal_fun in cal_sims' tiles (shard x shard, so a block that starts on a shard boundary holds the very scores cal_sims
+    would); one member: its scores as they are, several: their float64 mean, summed in member order and divided once, as
+    `_score_blocks` averages whole matrices.  members: (model, img_dev, cap_dev, lens)."""
+    def block(i0, i1):
+        acc = None
+        for (model, img, cap, lens), shard in zip(members, shard_sizes):
+            cal_fun = _cal_fun(model)
+            out = None
+            for r0 in range(i0, i1, shard):
+                r1 = min(r0 + shard, i1)
+                for j0 in range(0, n_cols, shard):
+                    j1 = min(j0 + shard, n_cols)
+                    with torch.no_grad():
+                        sim = cal_fun(img[r0:r1], cap[j0:j1], None if lens is None else lens[j0:j1], model.config).detach()
+                    if (r0, r1, j0, j1) == (i0, i1, 0, n_cols):
+                        out = sim
+                    else:
+                        if out is None:
+                            out = torch.empty(i1 - i0, n_cols, device=sim.device, dtype=sim.dtype)
+                        out[r0 - i0:r1 - i0, j0:j1] = sim
+            if len(members) == 1:
+                return out
+            acc = out.double() if acc is None else acc + out.double()
+        return acc / len(members)
+    return block
+
+
+def _hub_rows_per_block(rows, shard):
+    """Whole shards per block where a block holds at least one (the tiles are then cal_sims' own)."""
+    rows = max(1, int(rows))
+    return rows if rows < shard else rows // shard * shard
+
+
+class _RunningColumnLists(object):
+    """The k largest entries of every column over the row blocks folded so far, for CSLS' b.  fp32 blocks: `ops.topk_fold_cols`.
+    float64 blocks (ensemble means): the block's own final lists (`ops.topk_lists`) are put beside the running ones and the k
+    largest of the two taken again; only the VALUES reach the mean, so which of two equal scores is kept does not matter."""
+    def __init__(self, k):
+        self.k, self.state, self.vals, self.row0 = k, None, None, 0
+
+    def fold(self, S):
+        n = S.shape[0]
+        if S.dtype == torch.float32:
+            self.state = ops.topk_fold_cols(S, self.k, row0=self.row0, state=self.state)
+        else:
+            kb = min(self.k, n)
+            _, _, (_, val) = ops.topk_lists(S, kb, rows=False)
+            if self.vals is None:
+                self.vals = torch.full((S.shape[1], self.k), float('-inf'), device=S.device, dtype=torch.float64)
+            both = torch.cat([self.vals, val], 1)
+            _, self.vals, _ = ops.topk_lists(both, self.k, cols=False)
+        self.row0 += n
+
+    def mean(self):
+        if self.vals is not None:
+            return ops.hub_list_mean(self.vals, self.k)
+        _, val = ops.topk_merge_cols([self.state], self.k)
+        return ops.hub_list_mean(val, self.k)
+
+
+def hubness_bank_vectors(models_embs, bank_embs, method, k=10, beta=20.0, sl_img=slice(0, None, 5), sl_cap=slice(None), block_rows=640):
+    """The correction vectors from an EXTERNAL query bank (the usual choice: the train or dev split), whose score matrices may be
+    several times the gallery's and are never stored.  models_embs: list of (model, img_embs, cap_embs, cap_lens, shard_size) of
+    the gallery, as `_score_blocks` takes them (sl_img / sl_cap select the gallery's images and captions: a fold); bank_embs: list
+    of (img_embs, cap_embs, cap_lens) of the bank per model, in encode_data's layout (bank images = img_embs[::5]).
+      a [Ni]: from gallery-image x bank-caption scores -- rows are complete in a block: the fold's row_lse, or
+              `ops.topk_lists(rows=True)` then `ops.hub_list_mean`;
+      b [Nc]: from bank-image x gallery-caption scores -- row blocks go through `ops.hub_lse_fold`, or through
+              `ops.topk_fold_cols`, `ops.topk_merge_cols` and `ops.hub_list_mean`.
+    Both are scored in image-row blocks with the model's own cal_fun, ONE block on the device at a time: block_rows bank images for
+    b, and for a as many gallery images as give a block of the same number of scores (whole shards of the first model where a block
+    holds at least one: the tiles are then cal_sims' own).  Several models: the members' blocks are
+    averaged in float64 on the device before folding.  -> (a, b) float64 numpy."""
+    who = "hubness_bank_vectors"
+    _check_hubness(who, method, k, beta)
+    if len(bank_embs) != len(models_embs):
+        raise ValueError("%s: %d bank encodings for %d models" % (who, len(bank_embs), len(models_embs)))
+    dev = torch.device('cuda', torch.cuda.current_device())
+
+    def to_dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    shards = [m[4] for m in models_embs]
+    g_img = [to_dev(m[1][sl_img]) for m in models_embs]
+    g_cap = [to_dev(m[2][sl_cap]) for m in models_embs]
+    g_len = [None if m[3] is None else m[3][sl_cap] for m in models_embs]
+    q_img = [to_dev(q[0][::5]) for q in bank_embs]
+    q_cap = [to_dev(q[1]) for q in bank_embs]
+    q_len = [q[2] for q in bank_embs]
+    models = [m[0] for m in models_embs]
+    Ni, Nc, Qi, Qc = len(g_img[0]), len(g_cap[0]), len(q_img[0]), len(q_cap[0])
+    k = int(k)
+    if method == 'csls' and k > min(Qi, Qc):
+        raise ValueError("%s: k = %d is larger than a side of the bank (%d images, %d captions)" % (who, k, Qi, Qc))
+    block_rows = int(block_rows)
+    if block_rows < 1:
+        raise ValueError("%s: block_rows = %d < 1" % (who, block_rows))
+
+    # b: bank images x gallery captions, folded down the columns
+    score = _hub_block_scorer(list(zip(models, q_img, g_cap, g_len)), Nc, shards)
+    state, lists = None, _RunningColumnLists(k)
+    rows_b = _hub_rows_per_block(block_rows, shards[0])
+    for i0 in range(0, Qi, rows_b):
+        S = score(i0, min(i0 + rows_b, Qi))
+        if method == 'invsoftmax':
+            _, state = ops.hub_lse_fold(S, beta, state=state, rows=False)
+        else:
+            lists.fold(S)
+        del S
+    b = ops.hub_lse_cols(state, beta) if method == 'invsoftmax' else lists.mean()
+
+    # a: gallery images x bank captions, whole rows per block
+    score = _hub_block_scorer(list(zip(models, g_img, q_cap, q_len)), Qc, shards)
+    rows_a = _hub_rows_per_block(block_rows * Nc // max(Qc, 1), shards[0])
+    parts = []
+    for i0 in range(0, Ni, rows_a):
+        S = score(i0, min(i0 + rows_a, Ni))
+        if method == 'invsoftmax':
+            parts.append(ops.hub_lse_fold(S, beta, cols=False)[0])
+        else:
+            parts.append(ops.hub_list_mean(ops.topk_lists(S, k, cols=False)[1], k))
+        del S
+    a = torch.cat(parts)
+    return a.cpu().numpy(), b.cpu().numpy()
+
+
+def hubness_adjust(sims, a, b):
+    """S' = dtype((double(sims[i, j]) - a[i]) - b[j]) on the GPU (`ops.hub_adjust`), in the dtype of sims (float32 stays float32,
+    anything else is float64 as in `_ranks`); a / b: float64 vectors (numpy or tensors), None = zeros.  numpy's
+    ((sims.astype(float64) - a[:, None]) - b[None, :]).astype(dtype) is the same matrix bit for bit.  -> numpy array for numpy input,
+    a device tensor for a tensor."""
+    S = _device_matrix(sims)
+
+    def vec(v):
+        if v is None or torch.is_tensor(v):
+            return v if v is None else v.to(device=S.device, dtype=torch.float64)
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(v, dtype=np.float64))).to(S.device)
+    out = ops.hub_adjust(S, vec(a), vec(b))
+    return out if torch.is_tensor(sims) else out.cpu().numpy()
+
+
+def _hub_part(hub, sims, models_embs, sl_img, sl_cap, k, gt, prefix):
+    """One gallery (the whole split, or a fold): vectors -> adjusted matrix -> cal_recall, with the hub-tagged top-k lists and
+    ground-truth metrics beside it."""
+    method = hub['method']
+    if hub['bank'] is None:
+        a, b = hubness_vectors(sims, method, hub['k'], hub['beta'])
+    else:
+        a, b = hubness_bank_vectors(models_embs, hub['bank'], method, hub['k'], hub['beta'], sl_img, sl_cap)
+    adj = hubness_adjust(sims, a, b)
+    hub['vectors'][prefix + 'a'], hub['vectors'][prefix + 'b'] = a, b
+    if k > 0:
+        hub['lists'].update({prefix + key: v for key, v in topk(adj, k).items()})
+    if gt is not None:
+        hub['gt_result'] = gt_metrics(adj, gt['relation'])
+    print("--------------------- hubness-corrected (%s) ---------------------" % method)
+    return cal_recall(adj)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # evalrank_single / evalrank_ensemble (evaluation.py:262-435): checkpoint -> loader -> encode -> score -> rank ->
 # `<save_dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml`.
 _MEAN_KEYS = ('i2t_r1', 'i2t_r5', 'i2t_r10', 'i2t_medr', 'i2t_meanr', 't2i_r1', 't2i_r5', 't2i_r10', 't2i_medr', 't2i_meanr')
@@ -362,11 +559,13 @@ def _load_for_eval(model_path, data_path):
     return model, _config
 
 
-def _score_blocks(models_embs, fold5, k=0, lists=None, gt=None):
+def _score_blocks(models_embs, fold5, k=0, lists=None, gt=None, hub=None):
     """models_embs: list of (model, img_embs, cap_embs, cap_lens, shard_size); the similarity matrices of the
     models are averaged (ensemble, evaluation.py:377-381).  k > 0: the top-k lists of every (float64) matrix go into
     `lists` (fold5: keys PART_<i>_..., indices local to the part's matrix).  gt: {'path': FILE.npz} (not with fold5): the metrics
-    of that relation on the same matrix go into gt['result'], the relation into gt['relation']."""
+    of that relation on the same matrix go into gt['result'], the relation into gt['relation'].  hub: the state of a hubness
+    correction (`_evalrank`): the plain results are computed exactly as without it, and the corrected results of every gallery go
+    into hub['res'] (fold5: per fold, with vectors derived per fold)."""
     def sims_of(sl_img, sl_cap):
         acc = None
         for model, img, cap, lens, shard in models_embs:
@@ -382,23 +581,42 @@ def _score_blocks(models_embs, fold5, k=0, lists=None, gt=None):
         if gt is not None:
             gt['relation'] = _load_gt(gt['path'], sims.shape[0], sims.shape[1])
             gt['result'] = gt_metrics(sims, gt['relation'])
-        return cal_recall(sims)
+        res = cal_recall(sims)
+        if hub is not None:
+            hub['res'] = _hub_part(hub, sims, models_embs, slice(0, n, 5), slice(None), k, gt, '')
+        return res
     res_dic = {'sum_result': []}
+    if hub is not None:
+        hub['res'] = {'sum_result': []}
     for i in range(5):
         print(f"--------------------- The {i + 1} part ---------------------")
-        sims = sims_of(slice(i * 5000, (i + 1) * 5000, 5), slice(i * 5000, (i + 1) * 5000))
+        sl_img, sl_cap = slice(i * 5000, (i + 1) * 5000, 5), slice(i * 5000, (i + 1) * 5000)
+        sims = sims_of(sl_img, sl_cap)
         if k > 0:
             lists.update({f'PART_{i + 1}_{key}': v for key, v in topk(sims, k).items()})
         part = cal_recall(sims)
         res_dic[f'PART_{i + 1}'] = part
         res_dic['sum_result'] += part['result']
+        if hub is not None:
+            part = _hub_part(hub, sims, models_embs, sl_img, sl_cap, k, None, f'PART_{i + 1}_')
+            hub['res'][f'PART_{i + 1}'] = part
+            hub['res']['sum_result'] += part['result']
     res_dic['Mean_metrics'] = _mean_metrics(res_dic)
+    if hub is not None:
+        print("--------------------- hubness-corrected (%s) ---------------------" % hub['method'])
+        hub['res']['Mean_metrics'] = _mean_metrics(hub['res'])
     return res_dic
 
 
-def _evalrank(model_paths, data_path, split, fold5, tag, topk=0, gt=None):
+def _evalrank(model_paths, data_path, split, fold5, tag, topk=0, gt=None, hubness=None, hub_k=10, hub_beta=20.0, querybank='self'):
     import os
     import yaml
+    if hubness is not None:
+        _check_hubness("evalrank_" + tag, hubness, hub_k, hub_beta)
+        if not isinstance(querybank, str) or not querybank:
+            raise ValueError("evalrank_%s: querybank must be 'self' or the name of a split, got %r" % (tag, querybank))
+    elif querybank != 'self' or hub_k != 10 or hub_beta != 20.0:
+        raise ValueError("evalrank_%s: hub_k / hub_beta / querybank need hubness='csls' or 'invsoftmax'" % tag)
     if gt is not None and fold5:
         raise ValueError("gt does not combine with fold5: a ground-truth relation indexes ONE gallery, fold5 ranks five")
     gt = None if gt is None else {'path': gt}
@@ -417,7 +635,14 @@ def _evalrank(model_paths, data_path, split, fold5, tag, topk=0, gt=None):
         embs.append((model, img, cap, lens, cfg['batch_size'] * 5))
     print('#Images: %d, #Captions: %d' % (embs[0][1].shape[0] / 5, embs[0][2].shape[0]))
     lists = {}
-    res_dic = _score_blocks(embs, fold5, topk, lists, gt)
+    hub = None
+    if hubness is not None:
+        hub = {'method': hubness, 'k': int(hub_k), 'beta': float(hub_beta), 'bank': None, 'vectors': {}, 'lists': {}}
+        if querybank != 'self':                # the bank split through the same loader path, encoded by every model
+            print(f'Encoding the query bank : {querybank} ......')
+            bank_loader, _ = data.get_test_loader(querybank, _config['data_name'], _config['batch_size'], _config['workers'], _config)
+            hub['bank'] = [encode_data(model, bank_loader, islength=islength) for model, _ in loaded]
+    res_dic = _score_blocks(embs, fold5, topk, lists, gt, hub)
     res_dic['data_name'] = _config['data_name'] + ('_5fold' if fold5 else '')
     if len(model_paths) > 1 and fold5:
         res_dic['modal_path_1'], res_dic['modal_path_2'] = model_paths[0], model_paths[1]
@@ -429,7 +654,32 @@ def _evalrank(model_paths, data_path, split, fold5, tag, topk=0, gt=None):
         _save_topk(save_dir, res_dic['data_name'], tag, topk, lists)
     if gt is not None:
         _save_gt(save_dir, res_dic['data_name'], tag, gt['result'], gt['relation'])
+    if hub is not None:
+        _save_hub(save_dir, res_dic['data_name'], tag, hub, querybank, topk, gt)
     return res_dic
+
+
+def _save_hub(save_dir, data_name, tag, hub, querybank, topk, gt):
+    """`<data_name>_<tag>_hub_<method>_result.yaml` (cal_recall of the adjusted matrix and how it was corrected),
+    `..._hub_<method>.npz` (the vectors a and b; fold5: PART_<i>_-prefixed) and the hub-tagged counterparts of topk and gt."""
+    import os
+    import yaml
+    htag = f'{tag}_hub_{hub["method"]}'
+    out = dict(hub['res'])
+    out['data_name'] = data_name
+    out['hubness'] = hub['method']
+    out['hub_k' if hub['method'] == 'csls' else 'hub_beta'] = hub['k'] if hub['method'] == 'csls' else hub['beta']
+    out['querybank'] = querybank
+    if querybank == 'self':
+        out['comment'] = ('querybank self: the correction is derived from the evaluated queries themselves, so these numbers are '
+                          'transductive; name a held-out split (--querybank dev / train) for inductive ones')
+    with open(os.path.join(save_dir, f'{data_name}_{htag}_result.yaml'), 'w') as f:
+        yaml.safe_dump(_plain(out), f)
+    np.savez(os.path.join(save_dir, f'{data_name}_{htag}.npz'), **hub['vectors'])
+    if topk > 0:
+        _save_topk(save_dir, data_name, htag, topk, hub['lists'])
+    if gt is not None:
+        _save_gt(save_dir, data_name, htag, hub['gt_result'], gt['relation'])
 
 
 def _recall_dict(ranks):
@@ -482,19 +732,28 @@ def evalrank_fast(model_path, data_path=None, split='dev', fold5=False, comm=Non
     return res_dic
 
 
-def evalrank_single(model_path, data_path=None, split='dev', fold5=False, topk=0, gt=None):
+def evalrank_single(model_path, data_path=None, split='dev', fold5=False, topk=0, gt=None, hubness=None, hub_k=10, hub_beta=20.0,
+                    querybank='self'):
     """evaluation.py:262-335.  topk > 0: also `<data_name>[_5fold]_single_top<topk>.npz` next to the YAML (`topk`).
     gt: path of an `.npz` holding `pairs` [nnz, 2] (image, caption) and optionally n_images / n_captions, a ground-truth relation
     over the gallery (not with fold5): besides everything above, `<data_name>_single_gt_result.yaml` gets R@K, medr, meanr,
-    R-Precision and mAP@R of both directions under it and `<data_name>_single_gt_positions.npz` the arrays (`gt_metrics`)."""
-    return _evalrank([model_path], data_path, split, fold5, 'single', topk, gt)
+    R-Precision and mAP@R of both directions under it and `<data_name>_single_gt_positions.npz` the arrays (`gt_metrics`).
+    hubness: 'csls' (hub_k) or 'invsoftmax' (hub_beta): everything above is computed and written exactly as without it, and in
+    addition `<data_name>[_5fold]_single_hub_<method>_result.yaml` gets cal_recall of the hubness-corrected matrix
+    (`hubness_adjust`) with the method, its parameter and the query bank, and `..._single_hub_<method>.npz` the vectors a and b;
+    topk / gt also write `..._single_hub_<method>_top<topk>.npz` / `..._single_hub_<method>_gt_*` from the corrected matrix.
+    querybank: 'self' (the evaluated matrix itself: transductive) or a split ('dev', 'train') encoded through the same loader
+    (`hubness_bank_vectors`).  fold5 derives the vectors per fold."""
+    return _evalrank([model_path], data_path, split, fold5, 'single', topk, gt, hubness, hub_k, hub_beta, querybank)
 
 
-def evalrank_ensemble(model_path, model_path2, data_path=None, split='dev', fold5=False, topk=0, gt=None):
+def evalrank_ensemble(model_path, model_path2, data_path=None, split='dev', fold5=False, topk=0, gt=None, hubness=None, hub_k=10,
+                      hub_beta=20.0, querybank='self'):
     """evaluation.py:338-435: the two models' similarity matrices are averaged before ranking.  topk > 0: the top-k lists
     of the float64 average go to `<data_name>[_5fold]_ensemble_top<topk>.npz`.  gt: as evalrank_single, on the float64 average
-    -> `<data_name>_ensemble_gt_result.yaml` / `..._ensemble_gt_positions.npz`."""
-    return _evalrank([model_path, model_path2], data_path, split, fold5, 'ensemble', topk, gt)
+    -> `<data_name>_ensemble_gt_result.yaml` / `..._ensemble_gt_positions.npz`.  hubness / hub_k / hub_beta / querybank: as
+    evalrank_single, on the float64 average -> `<data_name>[_5fold]_ensemble_hub_<method>_result.yaml` / `..._ensemble_hub_<method>.npz`."""
+    return _evalrank([model_path, model_path2], data_path, split, fold5, 'ensemble', topk, gt, hubness, hub_k, hub_beta, querybank)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -1607,6 +1607,143 @@ def topk_fold_cols(S_block, k, row0=0, state=None):
     return state
 
 
+# ------------------------------------------------------------------------------------------ hubness correction (csrc/hubness.hip)
+def _hub_matrix(who, S):
+    """A 2-D float32 / float64 GPU matrix as the hubness kernels take it (a row-strided view is kept) -> (view, f64 flag)."""
+    if not torch.is_tensor(S):
+        raise TypeError("%s: S must be a torch tensor" % who)
+    if S.dim() != 2:
+        raise ValueError("%s: S must be 2-D, got shape %s" % (who, tuple(S.shape)))
+    if S.dtype not in (torch.float32, torch.float64):
+        if not S.is_cuda:
+            raise RuntimeError("S is on %s: the itr_amd ops only run on the GPU (no CPU fallback)" % S.device)
+        raise ValueError("%s: S must be float32 or float64, got %s" % (who, S.dtype))
+    return _dev_view(S, S.dtype), int(S.dtype == torch.float64)
+
+
+def _hub_beta(who, beta):
+    beta = float(beta)
+    if not (beta > 0.0 and np.isfinite(beta)):
+        raise ValueError("%s: beta = %r is not finite and positive" % (who, beta))
+    return beta
+
+
+def _hub_vector(who, name, t, n, dev):
+    if t is None:
+        return None
+    if not torch.is_tensor(t):
+        raise TypeError("%s: %s must be a torch tensor" % (who, name))
+    if not t.is_cuda:
+        raise RuntimeError("%s is on %s: the itr_amd ops only run on the GPU (no CPU fallback)" % (name, t.device))
+    if t.dtype != torch.float64 or tuple(t.shape) != (n,) or t.device != dev:
+        raise ValueError("%s: %s must be a float64 tensor of shape (%d,) on %s, got %s %s on %s"
+                         % (who, name, n, dev, t.dtype, tuple(t.shape), t.device))
+    return t.contiguous()
+
+
+def hub_lse_fold(S_block, beta, state=None, rows=True, cols=True):
+    """Fold ONE row block of a score matrix into the log-sum-exp statistics of the inverted softmax (csrc/hubness.hip), one pass
+    over the block for both directions.  S_block: float32 or float64 [n, Nc]; tensor rules of `topk_lists` (GPU only, a row-strided
+    view is taken as it is, any alignment).  beta: finite and positive.
+    -> (row_lse, state).  row_lse float64 [n] = (1 / beta) log sum_j exp(beta S[r, j]), final because a block holds whole rows
+    (None with rows=False).  state float64 [Nc, 2] = per column (running sum of exp(beta x - beta m), running maximum m) over
+    every block folded so far; a sum of 0 means empty, so zeros are the starting state (None starts there); a given state is
+    updated IN PLACE and returned (with cols=False it is returned untouched).  `hub_lse_cols(state, beta)` is the finishing step.
+    -inf entries add nothing, only -inf gives -inf, a +inf gives +inf, a NaN gives NaN (|beta S| >= 3.7e8 counts as +-inf).  No
+    atomics: the same call gives the same bits; another partition of the rows sums in another order and may differ in the last
+    bits."""
+    who = "hub_lse_fold"
+    lib = _lib.load()
+    S_, f64 = _hub_matrix(who, S_block)
+    beta = _hub_beta(who, beta)
+    n, Nc = S_.shape
+    dev = S_.device
+    if state is not None:
+        if not torch.is_tensor(state) or tuple(state.shape) != (Nc, 2) or state.dtype != torch.float64 or state.device != dev \
+                or not state.is_contiguous():
+            raise ValueError("hub_lse_fold: state must be a contiguous float64 tensor of shape (%d, 2) on %s" % (Nc, dev))
+    elif cols:
+        state = torch.zeros(Nc, 2, device=dev, dtype=torch.float64)
+    row_lse = torch.empty(n, device=dev, dtype=torch.float64) if rows else None
+    if n == 0 or Nc == 0 or not (rows or cols):
+        if rows and n:
+            row_lse.fill_(float('-inf'))       # a row without entries: the empty sum
+        return row_lse, state
+    wsb = lib.itr_hub_lse_workspace_bytes(n, Nc)
+    ws = torch.empty(wsb // 8 + 1, device=dev, dtype=torch.int64)
+    _lib.check(lib.itr_hub_lse_fold(_p(S_), f64, S_.stride(0), n, Nc, beta, _p(row_lse), _p(state if cols else None), _p(ws), wsb, _stream()))
+    return row_lse, state
+
+
+def hub_lse_cols(state, beta):
+    """The finishing step of `hub_lse_fold`: state float64 [Nc, 2] -> col_lse float64 [Nc] = m + log(sum) / beta, the log-sum-exp
+    of every column over all blocks folded into the state (-inf for an empty column; NaN / +inf where the state holds one).  The
+    state is left as it is: more blocks may be folded after the call."""
+    lib = _lib.load()
+    beta = _hub_beta("hub_lse_cols", beta)
+    if not torch.is_tensor(state):
+        raise TypeError("hub_lse_cols: state must be a torch tensor")
+    if not state.is_cuda:
+        raise RuntimeError("state is on %s: the itr_amd ops only run on the GPU (no CPU fallback)" % state.device)
+    if state.dim() != 2 or state.shape[1] != 2 or state.dtype != torch.float64 or not state.is_contiguous():
+        raise ValueError("hub_lse_cols: state must be a contiguous float64 tensor of shape (Nc, 2)")
+    Nc = state.shape[0]
+    col_lse = torch.empty(Nc, device=state.device, dtype=torch.float64)
+    if Nc:
+        _lib.check(lib.itr_hub_lse_finish(_p(state), Nc, beta, _p(col_lse), _stream()))
+    return col_lse
+
+
+def hub_list_mean(vals, k):
+    """The CSLS statistic of best-first lists: vals float32 or float64 [n, K] in the layout of row_val / col_val of `topk_lists`
+    and `topk_merge_cols` (GPU only; a row-strided view is taken as it is) -> float64 [n], 0.5 * mean of the first k entries of
+    every list, the mean being the float64 sum added best first one at a time, divided by k.  1 <= k <= K; k above TOPK_MAX is
+    NotImplementedError."""
+    who = "hub_list_mean"
+    lib = _lib.load()
+    V, f64 = _hub_matrix(who, vals)
+    k = int(k)
+    if k < 1:
+        raise ValueError("hub_list_mean: k = %d < 1" % k)
+    if k > TOPK_MAX:
+        raise NotImplementedError("hub_list_mean: k = %d above ITR_TOPK_MAX = %d" % (k, TOPK_MAX))
+    n, K = V.shape
+    if k > K:
+        raise ValueError("hub_list_mean: k = %d above the lists' length %d" % (k, K))
+    out = torch.empty(n, device=V.device, dtype=torch.float64)
+    if n:
+        _lib.check(lib.itr_hub_list_mean(_p(V), f64, n, V.stride(0), k, _p(out), _stream()))
+    return out
+
+
+def hub_adjust(S, a=None, b=None, out=None):
+    """The hubness-corrected matrix S'[i, j] = dtype((double(S[i, j]) - a[i]) - b[j]): two float64 subtractions, each rounded on
+    its own, then the cast to the dtype of S (float32 or float64) -- numpy reproduces it bit for bit.  S: [n, Nc], tensor rules of
+    `topk_lists` (GPU only, a row-strided view is taken as it is).  a float64 [n] / b float64 [Nc]: None means zeros.  a is
+    constant along a row and b along a column, so the i2t order is corrected by b alone and the t2i order by a alone: one matrix
+    serves both directions.  out: None allocates; `out is S` (or the same view) works in place; a tensor of the same shape and
+    dtype (any row stride) that does not overlap S is written; any other overlap is refused.  -> out."""
+    who = "hub_adjust"
+    lib = _lib.load()
+    S_, f64 = _hub_matrix(who, S)
+    n, Nc = S_.shape
+    dev = S_.device
+    a = _hub_vector(who, "a", a, n, dev)
+    b = _hub_vector(who, "b", b, Nc, dev)
+    if out is None:
+        out = torch.empty(n, Nc, device=dev, dtype=S_.dtype)
+    else:
+        if not torch.is_tensor(out) or tuple(out.shape) != (n, Nc) or out.dtype != S_.dtype or out.device != dev:
+            raise ValueError("hub_adjust: out must be a %s tensor of shape (%d, %d) on %s" % (S_.dtype, n, Nc, dev))
+        if Nc and n and (out.stride(1) != 1 or out.stride(0) < Nc):
+            raise ValueError("hub_adjust: out must have unit column stride and a row stride >= %d" % Nc)
+        if out.data_ptr() == S.data_ptr() and S_.data_ptr() != S.data_ptr():
+            raise ValueError("hub_adjust: in place needs S with unit column stride")
+    if n and Nc:
+        _lib.check(lib.itr_hub_adjust(_p(S_), f64, S_.stride(0), n, Nc, _p(a), _p(b), _p(out), out.stride(0), _stream()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ candidate lists (coarse-to-fine retrieval)
 # The list and pair plumbing every candidate op below shares (SCAN / SGRAF scores, SCAN / SGRAF explanations).  `who` is the public
 # function the messages name.

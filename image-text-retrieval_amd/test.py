@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Evaluate checkpoints like the reference's test.py:  python test.py MODEL_PATH [MODEL_PATH_2] [--data-path P]
-[--split test|testall|dev] [--fold5] [--topk K] [--gt FILE.npz] [--rerank K [--stream-coarse] [--explain M | --explain-sgraf M]]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
+[--split test|testall|dev] [--fold5] [--topk K] [--gt FILE.npz] [--hubness csls|invsoftmax [--hub-k K] [--hub-beta B] [--querybank SPLIT]] [--rerank K [--stream-coarse] [--explain M | --explain-sgraf M]]  ->  <run dir>/<data_name>[_5fold]_{single,ensemble}_result.yaml
 (and with --topk K the top-K retrieval lists of every query in <data_name>[_5fold]_{single,ensemble}_top<K>.npz).
 With --gt FILE.npz (`pairs` [nnz, 2] of (image, caption), optionally n_images / n_captions): a ground-truth relation with any number of
 positives per query  ->  also <data_name>_{single,ensemble}_gt_result.yaml (R@K, medr, meanr, R-Precision, mAP@R of both directions)
 and <data_name>_{single,ensemble}_gt_positions.npz (the position of every positive in its query's ranked list)
+With --hubness csls|invsoftmax: besides everything above, the matrix is corrected for hubs before ranking (S - a - b: CSLS with the mean of
+the --hub-k nearest, or the inverted softmax at --hub-beta; statistics of the evaluated matrix itself, or of the split --querybank names)
+->  also <data_name>[_5fold]_{single,ensemble}_hub_<method>_result.yaml and ..._hub_<method>.npz (the vectors a and b)
 python test.py COARSE_PATH FINE_PATH --rerank K: coarse-to-fine retrieval, the first model shortlists K candidates per query and the
 second (SCAN or SGRAF) scores only those  ->  <data_name>[_5fold]_rerank<K>_result.yaml and <data_name>[_5fold]_rerank<K>.npz
 With --explain M (SCAN fine model): also the word-by-region attention maps, per-word / per-region similarities and scores of the
@@ -47,7 +50,25 @@ if __name__ == "__main__":
     ap.add_argument("--stream-coarse", action="store_true",
                     help="with --rerank K and a pooled coarse model: the coarse similarity matrix is streamed in row blocks and never "
                          "stored (a gallery whose matrix does not fit); same files")
+    ap.add_argument("--hubness", choices=("csls", "invsoftmax"), default=None,
+                    help="also rank the hubness-corrected matrix S - a - b and write <data_name>_..._hub_<method>_result.yaml and "
+                         "..._hub_<method>.npz (the vectors); the plain results are written as without the flag")
+    ap.add_argument("--hub-k", type=int, default=None, metavar="K", help="with --hubness csls: neighbours in the mean (default 10)")
+    ap.add_argument("--hub-beta", type=float, default=None, metavar="B",
+                    help="with --hubness invsoftmax: the inverse temperature (default 20)")
+    ap.add_argument("--querybank", default=None, metavar="SPLIT",
+                    help="with --hubness: the split (dev, train) whose queries define the correction, encoded with the same loader; "
+                         "default: the evaluated split itself (transductive)")
     a = ap.parse_args()
+    if a.hubness is None and (a.hub_k is not None or a.hub_beta is not None or a.querybank is not None):
+        ap.error("--hub-k / --hub-beta / --querybank need --hubness csls|invsoftmax")
+    if a.hubness is not None and a.fast:
+        ap.error("--hubness does not combine with --fast: the sharded evaluation never holds a matrix to adjust")
+    if a.hubness is not None and a.rerank:
+        ap.error("--hubness does not combine with --rerank: the scores of coarse and fine lists are not comparable after a correction")
+    hub_kw = {} if a.hubness is None else {'hubness': a.hubness, 'hub_k': 10 if a.hub_k is None else a.hub_k,
+                                           'hub_beta': 20.0 if a.hub_beta is None else a.hub_beta,
+                                           'querybank': 'self' if a.querybank is None else a.querybank}
     if a.stream_coarse and not a.rerank:
         ap.error("--stream-coarse needs --rerank K")
     if a.explain is not None and not a.rerank:
@@ -83,7 +104,7 @@ if __name__ == "__main__":
         if dist.is_initialized():
             dist.destroy_process_group()
     elif len(a.model_path) == 1:
-        evaluation.evalrank_single(a.model_path[0], data_path=a.data_path, split=a.split, fold5=a.fold5, topk=a.topk, **gt_kw)
+        evaluation.evalrank_single(a.model_path[0], data_path=a.data_path, split=a.split, fold5=a.fold5, topk=a.topk, **gt_kw, **hub_kw)
     else:
         evaluation.evalrank_ensemble(a.model_path[0], a.model_path[1], data_path=a.data_path, split=a.split, fold5=a.fold5,
-                                     topk=a.topk, **gt_kw)
+                                     topk=a.topk, **gt_kw, **hub_kw)

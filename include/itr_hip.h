@@ -541,6 +541,38 @@ size_t itr_topk_fold_workspace_bytes(int64_t n_rows_local, int64_t Nc, int K);
 int itr_topk_fold_cols(const float *S, int64_t ldS, int64_t row0, int64_t n_rows_local, int64_t Nc, int K,
                        uint64_t *col_key, float *col_val, void *workspace, size_t workspace_bytes, itr_stream_t stream);
 
+/* ---- hubness correction before ranking: CSLS and inverted softmax (csrc/hubness.hip) ----
+ * Both corrections subtract a per-image and a per-caption vector, S'[i, j] = S[i, j] - a[i] - b[j]; a is constant along a row and
+ * b along a column, so one adjusted matrix serves both directions and every consumer above works on it unchanged.  The vectors
+ * are reductions over score matrices that may be query banks, scored in row blocks and never stored.  float64 throughout; S is
+ * float32 (f64 = 0) or float64 (f64 = 1), leading dimension ldS >= Nc with any alignment.
+ * itr_hub_lse_fold: one pass over the row block S [n_rows, Nc], every element read once and widened to double.
+ *   row_lse [n_rows] (may be NULL): (1 / beta) log sum_j exp(beta S[r, j]); final, a block holds whole rows.
+ *   col_state [Nc][2] (may be NULL), read AND written: per column (running sum of exp(beta x - beta m), running maximum m) over
+ *     every block folded so far.  A sum of 0 means empty whatever the second slot holds: all-zero bytes are the starting state.
+ *     A state whose maximum is NaN or +inf stands for that result and carries sum 1.
+ *   -inf entries add nothing; only -inf gives -inf; a +inf gives +inf; a NaN gives NaN (np.logaddexp.reduce's results).
+ *   Scores beyond any similarity's range, |beta S| >= 2^29 ln 2 = 3.7e8, count as +-inf.
+ *   No floating-point atomics: partial sums go to the workspace and are combined in a fixed order, so the same call on the same
+ *   inputs gives the same bits however the workgroups are scheduled.  Other row partitions may differ in the last bits.
+ *   No host read-back and no allocation inside the call.  workspace: itr_hub_lse_workspace_bytes(n_rows, Nc) bytes, 8-byte aligned.
+ * itr_hub_lse_finish: col_lse[j] = m_j + log(sum_j) / beta of a state (-inf for an empty column).
+ * itr_hub_list_mean: out[r] = 0.5 * (float64 sum of the first k entries of list r, added best first one at a time) / k, for n
+ *   best-first lists val [n, ld >= k] in the layout of row_val / col_val of itr_topk, itr_topk_merge and itr_topk_f64.
+ * itr_hub_adjust: out[i, j] = dtype((double(S[i, j]) - a[i]) - b[j]): two float64 subtractions, each rounded on its own, nothing
+ *   contracted or reassociated, then the cast to the dtype of S.  a [n_rows] or b [Nc] may be NULL (zeros).  out == S with
+ *   ldo == ldS works in place; any other overlap of out with S, a or b is refused ("alias").
+ * beta not finite and positive, k < 1, null pointers, ldS < Nc, negative sizes -> ITR_ERR_BADARG; k > ITR_TOPK_MAX ->
+ * ITR_ERR_UNSUPPORTED; empty shapes -> ITR_OK, nothing written.  Every argument check comes before any device call.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+size_t itr_hub_lse_workspace_bytes(int64_t n_rows, int64_t Nc);
+int itr_hub_lse_fold(const void *S, int f64, int64_t ldS, int64_t n_rows, int64_t Nc, double beta, double *row_lse,
+                     double *col_state, void *workspace, size_t workspace_bytes, itr_stream_t stream);
+int itr_hub_lse_finish(const double *col_state, int64_t Nc, double beta, double *col_lse, itr_stream_t stream);
+int itr_hub_list_mean(const void *val, int f64, int64_t n, int64_t ld, int k, double *out, itr_stream_t stream);
+int itr_hub_adjust(const void *S, int f64, int64_t ldS, int64_t n_rows, int64_t Nc, const double *a, const double *b, void *out,
+                   int64_t ldo, itr_stream_t stream);
+
 /* ---- a6 on candidate lists: xattn_score_t2i / xattn_score_i2t (Objectives.py:329-476) for LISTED (image, caption) pairs ----
  * The fine stage of coarse-to-fine retrieval: only the P listed pairs are scored (csrc/scan_pairs.hip), with the arithmetic of
  * itr_scan_xattn_scores (exact fp32 dot products, Gram-form cosine; same mode / norm / agg codes, lambda_softmax, lambda_lse).
