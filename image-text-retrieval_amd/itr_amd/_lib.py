@@ -81,6 +81,9 @@ SIGNATURES = {
     "itr_infonce_workspace_bytes": (sz, [i32]),
     "itr_infonce_fwd": (i32, [vp, vp, i32, i64, f32, vp, vp, vp, vp, vp]),
     "itr_infonce_bwd": (i32, [vp, vp, i32, i64, f32, vp, vp, vp, vp, i64, vp]),
+    "itr_distill_workspace_bytes": (sz, [i32]),
+    "itr_distill_fwd": (i32, [vp, vp, i32, i64, i64, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "itr_distill_bwd": (i32, [vp, vp, i32, i64, i64, f32, f32, vp, vp, vp, vp, vp, vp, i64, vp]),
     "itr_xbm_workspace_bytes": (sz, [i32, i32]),
     "itr_xbm_hinge_fwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp]),
     "itr_xbm_hinge_bwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp]),

@@ -40,7 +40,12 @@ DEFAULTS = dict(
     # not keys of the reference: memory_bank=M > 0 keeps the last M detached (image, caption) embeddings of the steps (VSE++, VSRN,
     # SAEM) and ranks every query against batch u memory (itr_amd/membank.py, ops.xbm_hinge_loss / xbm_infonce_loss).
     # The memory is pushed every step and used once Eiters > memory_start.  Training switches like `loss`; 0 is the step as it was
-    memory_bank=0, memory_start=0)
+    memory_bank=0, memory_start=0,
+    # not keys of the reference: distill_teacher=<checkpoint of a SCAN or SGRAF model> trains a VSE++ or VSRN student to reproduce that
+    # fine model's ranking distribution over every batch, next to its own hinge / InfoNCE loss: loss + distill_weight *
+    # ops.distill_loss(scores / distill_temperature, teacher scores / distill_teacher_temperature).  '' is off: the step
+    # as it was.  The weight and the two temperatures are untuned defaults.  Training switches like `loss`
+    distill_teacher='', distill_weight=1.0, distill_temperature=0.05, distill_teacher_temperature=0.05)
 
 NAMED = {
     'VSE_PP': dict(name="VSE++", data_name="f30k_precomp", vocab_type='pkl', val_step=10, img_dim=4096,

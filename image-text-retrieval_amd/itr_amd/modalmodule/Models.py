@@ -42,6 +42,8 @@ class base_module(nn.Module):
         self.memory = None               # the cross-batch memory (membank.MemoryBank), made by the first step with memory_bank > 0
         self._xbm_pending = None         # the step's rows, pushed once its backward has run
         self._xbm_config()
+        object.__setattr__(self, 'distill_teacher', None)      # a frozen fine model (attach_distill_teacher); never a registered submodule
+        self._distill_config()
 
     def calculate_params(self):
         self.params_num = sum(p.numel() for p in self.params)
@@ -181,6 +183,69 @@ class base_module(nn.Module):
         self._xbm_pending = (img.detach(), cap.detach(), own)
         return loss
 
+    # ---- score distillation from a fine teacher
+    distill_student = False              # True in the pooled GRU-text families that --rerank accepts as coarse (VSE++, VSRN)
+
+    def _distill_config(self):
+        """The distill_* keys are refused here, when the model is built, if they cannot mean anything.  distill_teacher = '' (the
+        default, and every configuration read from an old checkpoint) is off; the teacher itself is attached after the build."""
+        cfg = self.config
+        w = cfg.get('distill_weight', 1.0)
+        if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)) or not np.isfinite(w) or w <= 0:
+            raise ValueError("distill_weight must be finite and > 0, got %r" % (w,))
+        ops._distill_scale(cfg.get('distill_temperature', 0.05), "distill_temperature")
+        ops._distill_scale(cfg.get('distill_teacher_temperature', 0.05), "distill_teacher_temperature")
+        path = cfg.get('distill_teacher', '')
+        if not isinstance(path, str):
+            raise ValueError("distill_teacher must be a checkpoint path or '' (off), got %r" % (path,))
+        if path:
+            self._distill_student_check("distill_teacher=%r" % path)
+
+    def _distill_student_check(self, what):
+        if not self.distill_student:
+            raise ValueError("%s: %s cannot be a distillation student (VSE++ and VSRN can: the pooled GRU-text models a reranking "
+                             "pipeline takes as its coarse stage; SAEM / CAMERA batches carry BERT tokens, SCAN / SGRAF are teachers)"
+                             % (what, type(self).__name__))
+        M = self.config.get('memory_bank', 0)
+        if M > 0:
+            raise ValueError("%s together with memory_bank=%d: the teacher scores the batch only, not the memory" % (what, M))
+
+    def attach_distill_teacher(self, teacher):
+        """Make `teacher` (a built SCAN or SGRAF model, or None to detach) the fine model whose scores of every training batch this
+        model is distilled from.  The teacher is only ever run under no_grad in evaluation mode; it is no submodule of this model and
+        no part of state_dict() or of a checkpoint."""
+        if teacher is not None:
+            self._distill_student_check("a distillation teacher")
+            name = teacher.config.get('name') if isinstance(teacher, base_module) else None
+            if not isinstance(teacher, (SCAN, SGRAF)) or name not in ('SCAN', 'SGRAF'):
+                raise ValueError("a distillation teacher must be a SCAN or SGRAF model, got %s" % (type(teacher).__name__,))
+            for key in ('vocab_size', 'img_dim'):
+                if teacher.config.get(key) != self.config.get(key):
+                    raise ValueError("distillation: the teacher's %s=%r differs from the student's %s=%r: both read the same batch"
+                                     % (key, teacher.config.get(key), key, self.config.get(key)))
+        object.__setattr__(self, 'distill_teacher', teacher)
+
+    def _distill(self, loss, scores, images, captions, lengths, comm):
+        """`loss` (what _hinge / _hinge_memory returned) when no teacher is attached.  Otherwise the teacher scores the step's own batch
+        -- evaluation mode, no_grad, forward_emb then its dense scorer (evaluation._cal_fun) -- and distill_weight * ops.distill_loss of
+        the student's `scores` against them is added; the unweighted term is logged as 'Distill'."""
+        teacher = self.distill_teacher
+        if teacher is None:
+            return loss
+        if comm is not None and comm.on:
+            raise ValueError("a distillation teacher under data parallelism (%d ranks): the teacher would have to score the global "
+                             "batch on every rank; distillation is built for one process only" % comm.world)
+        from ..metricmodule.evaluation import _cal_fun
+        cfg = self.config
+        teacher.val_start()
+        with torch.no_grad():
+            emb = teacher.forward_emb(images, captions, lengths)
+            target = _cal_fun(teacher)(emb[0], emb[1], lengths, teacher.config)
+        term = ops.distill_loss(scores, target.detach().to(torch.float32), cfg.get('distill_temperature', 0.05),
+                                cfg.get('distill_teacher_temperature', 0.05))
+        self._log('Distill', term.detach(), scores.size(0))
+        return loss + cfg.get('distill_weight', 1.0) * term
+
     def _hinge_groups(self, ids, comm):
         """config['mask_same_image'] off (the default, and every configuration read from an old checkpoint): None.  On: the image of
         every pair, ids // train_im_div (host array), in the ROW ORDER OF THE SCORE MATRIX the step hands to the hinge -- the batch
@@ -233,6 +298,7 @@ class VSE_PP(base_module):
     -> fc -> l2norm; text = last valid GRU state -> l2norm; honours bi_gru."""
 
     xbm_supported = True
+    distill_student = True
 
     def __init__(self, config):
         super().__init__(config)
@@ -278,6 +344,7 @@ class VSE_PP(base_module):
             else:
                 scores = pair_scores(img, cap)
             loss = self._hinge_memory(img, cap, scores, ids, pair_scores, groups, comm)
+            loss = self._distill(loss, scores, images, captions, lengths, comm)
             self._step(loss, scores.size(0))
 
     def forward_loss(self, img_emb, cap_emb):
@@ -349,6 +416,7 @@ class VSRN(base_module):
     model is never saved) -- the same here."""
 
     xbm_supported = True
+    distill_student = True
 
     def __init__(self, config, use_txt_emb=True):
         super().__init__(config)
@@ -447,6 +515,7 @@ class VSRN(base_module):
             pair_scores = ag.order_scores if self.config['measure'] == 'order' else ag.cosine_scores
             scores = pair_scores(img, cap)
             retrieval_loss = self._hinge_memory(img, cap, scores, ids, pair_scores, groups, comm)
+            retrieval_loss = self._distill(retrieval_loss, scores, images, captions, lengths, comm)
             caption_loss = self.caption_model.caption_loss_train(gcn_emb, captions, self._dev(captions_mask), self._seeds,
                                                                  self.caption_model.training, batch_total=n_batch)
             caption_total = caption_loss.detach()

@@ -507,6 +507,93 @@ def infonce_loss(scores, temperature=0.05, groups=None):
     return _InfoNCEFn.apply(scores, temperature, groups)
 
 
+# ---- score distillation: a student's B x B matrix towards a teacher's ranking distribution over the batch (csrc/distill.hip)
+def _distill_scale(temperature, which):
+    """float32(1 / temperature) of the student's or the teacher's scores, checked like _infonce_scale."""
+    t = float(temperature)
+    if not np.isfinite(t) or t <= 0.0:
+        raise ValueError("distillation loss: %s must be finite and positive, got %r" % (which, temperature))
+    with np.errstate(over='ignore', under='ignore'):
+        scale = float(np.float32(1.0 / t))
+    if not np.isfinite(scale) or scale <= 0.0:
+        raise ValueError("distillation loss: 1 / %s does not fit float32 for %s %r" % (which, which, temperature))
+    return scale
+
+
+def _distill_operands(scores, teacher_scores):
+    """Checked (scores, teacher_scores): equal square shapes (refused before the device is asked for), fp32, contiguous, one device."""
+    if torch.is_tensor(scores) and (scores.dim() != 2 or scores.shape[0] != scores.shape[1]):
+        raise ValueError("distillation loss needs a square score matrix, got %s" % (tuple(scores.shape),))
+    if torch.is_tensor(scores) and torch.is_tensor(teacher_scores) and teacher_scores.shape != scores.shape:
+        raise ValueError("distillation loss: teacher scores %s do not match the student's %s" % (tuple(teacher_scores.shape), tuple(scores.shape)))
+    scores, teacher_scores = _dev(scores, name="scores"), _dev(teacher_scores, name="teacher_scores")
+    if teacher_scores.device != scores.device:
+        raise ValueError("distillation loss: teacher scores on %s, student scores on %s" % (teacher_scores.device, scores.device))
+    return scores, teacher_scores
+
+
+def distill_fwd(scores, teacher_scores, temperature=0.05, teacher_temperature=0.05):
+    """-> (loss[1], row_lse_s[B], col_lse_s[B], row_lse_t[B], col_lse_t[B]) of itr_distill_fwd: the mean over the B rows and the B columns
+    of KL(softmax(teacher_scores / teacher_temperature) || softmax(scores / temperature)), and the log-sum-exps its backward reads."""
+    lib = _lib.load()
+    scores, teacher_scores = _distill_operands(scores, teacher_scores)
+    scale_s = _distill_scale(temperature, "temperature")
+    scale_t = _distill_scale(teacher_temperature, "teacher_temperature")
+    B = scores.shape[0]
+    loss = torch.empty(1, device=scores.device, dtype=torch.float32)
+    lse = [torch.empty(B, device=scores.device, dtype=torch.float32) for _ in range(4)]
+    ws = torch.empty(max(1, int(lib.itr_distill_workspace_bytes(B))), device=scores.device, dtype=torch.uint8)
+    _lib.check(lib.itr_distill_fwd(_p(scores), _p(teacher_scores), B, B, B, scale_s, scale_t, _p(loss), _p(lse[0]), _p(lse[1]), _p(lse[2]),
+                                   _p(lse[3]), _p(ws), _stream()))
+    return (loss,) + tuple(lse)
+
+
+def distill_bwd(scores, teacher_scores, temperature, teacher_temperature, row_lse_s, col_lse_s, row_lse_t, col_lse_t, grad_loss):
+    """dS of distill_fwd from its four saved log-sum-exp vectors (itr_distill_bwd)."""
+    lib = _lib.load()
+    scores, teacher_scores = _distill_operands(scores, teacher_scores)
+    scale_s = _distill_scale(temperature, "temperature")
+    scale_t = _distill_scale(teacher_temperature, "teacher_temperature")
+    B = scores.shape[0]
+    g = _dev(grad_loss.reshape(1), name="grad_loss")
+    lse = [_dev(v, name=n) for v, n in ((row_lse_s, "row_lse_s"), (col_lse_s, "col_lse_s"), (row_lse_t, "row_lse_t"), (col_lse_t, "col_lse_t"))]
+    if any(v.shape != (B,) for v in lse):
+        raise ValueError("distillation loss: the four log-sum-exp vectors must have length %d" % B)
+    dS = torch.empty_like(scores)
+    _lib.check(lib.itr_distill_bwd(_p(scores), _p(teacher_scores), B, B, B, scale_s, scale_t, _p(lse[0]), _p(lse[1]), _p(lse[2]), _p(lse[3]),
+                                   _p(g), _p(dS), B, _stream()))
+    return dS
+
+
+class _DistillFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, teacher_scores, temperature, teacher_temperature):
+        scores, teacher_scores = scores.contiguous(), teacher_scores.contiguous()
+        out = distill_fwd(scores, teacher_scores, temperature, teacher_temperature)
+        ctx.save_for_backward(scores, teacher_scores, *out[1:])
+        ctx.temperature, ctx.teacher_temperature = temperature, teacher_temperature
+        return out[0].reshape(())
+
+    @staticmethod
+    def backward(ctx, grad):
+        scores, teacher_scores, rls, cls, rlt, clt = ctx.saved_tensors
+        dS = distill_bwd(scores, teacher_scores, ctx.temperature, ctx.teacher_temperature, rls, cls, rlt, clt, grad.contiguous())
+        return dS, None, None, None
+
+
+def distill_loss(scores, teacher_scores, temperature=0.05, teacher_temperature=0.05):
+    """Differentiable (w.r.t. scores) score-distillation loss, HIP forward and backward: the KL divergence from the teacher's softmax over
+    teacher_scores / teacher_temperature to the student's over scores / temperature, along every row (image-to-text) and every column
+    (text-to-image) of the batch, averaged.  There is no group mask: the teacher's scores say which other captions are positives.
+    `teacher_scores` is a target, not a variable: one that requires grad is refused."""
+    if torch.is_tensor(teacher_scores) and teacher_scores.requires_grad:
+        raise ValueError("distillation loss: teacher_scores must not require grad (score the teacher under torch.no_grad(), or detach)")
+    _distill_scale(temperature, "temperature")
+    _distill_scale(teacher_temperature, "teacher_temperature")
+    scores, teacher_scores = _distill_operands(scores, teacher_scores)
+    return _DistillFn.apply(scores, teacher_scores, temperature, teacher_temperature)
+
+
 # ---- cross-batch memory: both losses on batch u memory (csrc/xbm_loss.hip)
 def _xbm_operands(who, S, R, C, groups, bank_groups):
     """Checked (S [B, B], R [B, n], C [n, B], groups int32 [B], bank_groups int32 [n]) on S's device."""

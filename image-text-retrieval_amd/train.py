@@ -38,6 +38,11 @@ def train(_config):
     # own figure on that path, the PrecompDataset's on the DataLoader path
     resident_set = getattr(train_loader, 'resident_set', None)
     model.train_im_div = int(resident_set.im_div if resident_set is not None else train_loader.dataset.im_div)
+    if _config.get('distill_teacher', ''):
+        # the fine model the student is distilled from: loaded the way test.py loads a model, frozen, kept out of the checkpoints
+        from itr_amd.metricmodule.evaluation import _load_for_eval
+        teacher, _ = _load_for_eval(_config['distill_teacher'], None)
+        model.attach_distill_teacher(teacher)
     for epoch in range(start_epoch, _config['num_epochs']):
         utils.adjust_learning_rate(_config, model.optimizer, epoch)
         best_rsum, best_r1 = utils.train_step(_config, train_loader, model, epoch, val_loader, best_rsum, best_r1)
@@ -54,10 +59,18 @@ def train(_config):
         dist.destroy_process_group()
 
 
+def refuse_distributed_distillation(cfg):
+    """distill_teacher under WORLD_SIZE > 1 is refused before any process group, directory or loader is made."""
+    if cfg.get('distill_teacher', '') and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("distill_teacher=%r under WORLD_SIZE=%s: distillation is built for one process only (the teacher would have "
+                         "to score the global batch on every rank)" % (cfg['distill_teacher'], os.environ["WORLD_SIZE"]))
+
+
 def main(argv):
     # one process per GPU; several ranks may share a device only under the gloo test backend
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     cfg = cfgmod.build_config(argv)
+    refuse_distributed_distillation(cfg)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # data-parallel training: `python -m torch.distributed.run --nproc-per-node N train.py with ...`.  Every rank
         # builds the same loaders (same seed => same global batches) and train_emb shards each batch; rank 0 makes the

@@ -225,6 +225,37 @@ int itr_infonce_fwd(const float *S, const int32_t *group /* or NULL */, int B, i
 int itr_infonce_bwd(const float *S, const int32_t *group /* or NULL */, int B, int64_t ldS, float scale, const float *row_lse,
                     const float *col_lse, const float *grad_loss, float *dS, int64_t lddS, itr_stream_t stream);
 
+/* ---- Score distillation on the same B x B matrix: the student's scores S are pulled towards the ranking distribution of a teacher's
+ * scores T [B, B] over the same batch (T carries no gradient), row-wise and column-wise.  The entry stands
+ * next to ContrastiveLoss.forward (Objectives.py:93-115) and replaces no reference line.
+ *   scale_s = float32(1 / distill_temperature), scale_t = float32(1 / distill_teacher_temperature),
+ *   z_s = scale_s * S, z_t = scale_t * T (one fp32 product each).
+ *     p_row[i,:] = softmax_j z_t[i,:]     q_row[i,:] = softmax_j z_s[i,:]
+ *     p_col[:,j] = softmax_i z_t[:,j]     q_col[:,j] = softmax_i z_s[:,j]
+ *     KL_row[i] = sum_j p_row[i,j] (z_t[i,j] - z_s[i,j]) - lse_t_row[i] + lse_s_row[i]
+ *     KL_col[j] = sum_i p_col[i,j] (z_t[i,j] - z_s[i,j]) - lse_t_col[j] + lse_s_col[j]
+ *     loss = ( sum_i KL_row[i] + sum_j KL_col[j] ) / (2 B)
+ *     dS[i,j] = g scale_s / (2 B) ( (q_row - p_row)[i,j] + (q_col - p_col)[i,j] );   g = grad_loss[0] (device scalar, as in the hinge).
+ *   There is no group mask: every row and column runs over the whole batch.  The teacher scores the other captions of an image highly,
+ *   so they become soft positives and need no mask.
+ *   The two log-sum-exps of a row or column are subtracted from each other first, then from the cross term.  With T bit-equal to S and
+ *   scale_t == scale_s the loss is bit-zero and dS is bit-zero; B = 1 gives loss 0 and dS 0.
+ * fwd is one pass over both matrices (a running (max, sum) pair for z_s and a (max, sum, weighted sum) triple for z_t per row and column)
+ * plus a finishing workgroup; it writes loss[0] and the four log-sum-exp vectors row_lse_s[B], col_lse_s[B], row_lse_t[B], col_lse_t[B]
+ * (fp32, kept for the backward) and needs itr_distill_workspace_bytes(B) bytes of scratch (0 for B <= 0; linear in B).  bwd is one
+ * launch that writes every entry of dS once from the four saved vectors.  Deterministic: no float atomics, the 2B terms are summed in a
+ * fixed order in float64, two runs give the same bits.  S and T are read in whole 256-byte row segments by the row pass and by the
+ * column pass alike.  B is not limited to a multiple of anything; ldS, ldT and lddS may exceed B.
+ * Host checks before anything touches the device (ITR_ERR_BADARG, "itr_distill_fwd: ..." / "itr_distill_bwd: ..."): a null pointer,
+ * B < 1, ldS < B, ldT < B, lddS < B, scale_s or scale_t not finite or <= 0.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+size_t itr_distill_workspace_bytes(int B);
+int itr_distill_fwd(const float *S, const float *T, int B, int64_t ldS, int64_t ldT, float scale_s, float scale_t, float *loss,
+                    float *row_lse_s, float *col_lse_s, float *row_lse_t, float *col_lse_t, void *workspace, itr_stream_t stream);
+int itr_distill_bwd(const float *S, const float *T, int B, int64_t ldS, int64_t ldT, float scale_s, float scale_t,
+                    const float *row_lse_s, const float *col_lse_s, const float *row_lse_t, const float *col_lse_t,
+                    const float *grad_loss, float *dS, int64_t lddS, itr_stream_t stream);
+
 /* ---- Cross-batch memory (XBM): the two losses above on batch u memory.  S [B, B] is the step's matrix (image i vs caption j); R [B, n]
  * scores image i against memory caption k and C [n, B] memory image k against caption j, the memory being n detached (image, caption)
  * embeddings of earlier steps.  Row i's candidates are S[i, :] then R[i, :], column j's are S[:, j] then C[:, j]; a candidate index

@@ -115,7 +115,7 @@ def oracle_cpu_step(model_name, batch, cfg, model=None):
     return time.perf_counter() - t0
 
 
-def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=None, mask_same_image=False, cross_attn='t2i', loss='hinge', memory_bank=0):
+def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=None, mask_same_image=False, cross_attn='t2i', loss='hinge', memory_bank=0, distill=None):
     from itr_amd import config as C
     from itr_amd.modalmodule import get_model
     from itr_amd.metricmodule.evaluation import LogCollector
@@ -131,6 +131,11 @@ def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=N
         cfg.update(bert_config_file=cfg_file, init_checkpoint=ckpt, trans_cfg=trans, vocab_size=30522, batch_size=batch)
     torch.manual_seed(0)
     model = get_model(cfg)
+    if distill:
+        # a teacher of the reference's shape with fresh weights (the cost of a step does not depend on them); SGRAF: the SAF module
+        tcfg = C.build_config(['with', distill, 'data_name=coco_precomp', 'bi_gru=True'] + (['module_name=SAF'] if distill == 'SGRAF' else []))
+        tcfg['vocab_size'], tcfg['img_dim'] = V_COCO, 2048
+        model.attach_distill_teacher(get_model(tcfg))
     model.train_im_div = 5           # the precomp splits' captions per image; the batches' ids are 0 .. B-1, so the mask has groups of 5
     model.train_start()
     model.logger = LogCollector()
@@ -171,7 +176,7 @@ def run(model_name, module=None, batch=128, steps=10, warmup=3, cpu=False, dev=N
     meter = model.logger.meters['Loss' if 'Loss' in model.logger.meters else 'Loss1']
     row = {"family": name, "batch": batch, "words": int(sum(lens)), "steps": steps, "warmup": warmup, "ms_per_step": round(dt * 1e3, 3),
            "pairs_per_s": round(batch * batch / dt, 1), "forward_ms": round(float(split[0]), 3), "backward_ms": round(float(split[1]), 3),
-           "optimizer_ms": round(float(split[2]), 3), "loss": round(float(meter.val), 4), "loss_kind": loss, "memory_bank": memory_bank,
+           "optimizer_ms": round(float(split[2]), 3), "loss": round(float(meter.val), 4), "loss_kind": loss, "memory_bank": memory_bank, "distill": distill or "",
            "reference": "Models.py train_emb (:115-145, :205-225, :444-464, :518-546, :606-645); utils.py:80-102 times each batch"}
     if fm is not None:
         row["flop_model"] = fm
@@ -221,6 +226,7 @@ def main():
     ap.add_argument("--mask-same-image", action="store_true", help="time the step with mask_same_image=True (the hinge with the group mask)")
     ap.add_argument("--memory-bank", type=int, default=0, help="time the step with a cross-batch memory of this many pairs, filled before the timed steps (config key `memory_bank`; VSE_PP, VSRN, SAEM)")
     ap.add_argument("--loss", default="hinge", choices=["hinge", "infonce"], help="the ranking loss of the step (config key `loss`; infonce at the default temperature)")
+    ap.add_argument("--distill", default=None, choices=["SCAN", "SGRAF"], help="time the step with a distillation teacher of this family attached (reference shape, fresh weights; students: VSE_PP, VSRN)")
     ap.add_argument("--cross-attn", default="t2i", choices=["t2i", "i2t"], help="SCAN: the direction of the cross attention")
     a = ap.parse_args()
     t_start = time.perf_counter()
@@ -232,7 +238,7 @@ def main():
             rows[name] = {"error": "not started: the time budget of the run was spent"}
             continue
         try:
-            r = run(model_name, module, a.batch or batch, a.steps, a.warmup, cpu=a.cpu, mask_same_image=a.mask_same_image, cross_attn=a.cross_attn, loss=a.loss, memory_bank=a.memory_bank)
+            r = run(model_name, module, a.batch or batch, a.steps, a.warmup, cpu=a.cpu, mask_same_image=a.mask_same_image, cross_attn=a.cross_attn, loss=a.loss, memory_bank=a.memory_bank, distill=a.distill)
         except Exception as e:      # noqa: BLE001  (one family must not take the others' rows with it)
             r = {"family": name, "error": "%s: %s" % (type(e).__name__, e)}
         rows[name] = r
