@@ -129,6 +129,8 @@ SIGNATURES = {
     "itr_topk_f64": (i32, [vp, i64, i64, i64, i32, vp, vp, vp, vp, vp]),
     "itr_topk_fold_workspace_bytes": (sz, [i64, i64, i32]),
     "itr_topk_fold_cols": (i32, [vp, i64, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
+    "itr_search_topk_workspace_bytes": (sz, [i64, i64, i32, i32]),
+    "itr_search_topk": (i32, [vp, i64, i64, vp, i64, i64, i64, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
     "itr_hub_lse_workspace_bytes": (sz, [i64, i64]),
     "itr_hub_lse_fold": (i32, [vp, i32, i64, i64, i64, C.c_double, vp, vp, vp, sz, vp]),
     "itr_hub_lse_finish": (i32, [vp, i64, C.c_double, vp, vp]),

@@ -1694,6 +1694,53 @@ def topk_fold_cols(S_block, k, row0=0, state=None):
     return state
 
 
+SEARCH_MAX_QUERIES = 64    # ITR_SEARCH_MAX_QUERIES (include/itr_hip.h)
+SEARCH_MAX_SLABS = 1024    # ITR_SEARCH_MAX_SLABS
+
+
+def search_topk(queries, gallery, k, row0=0, n_slabs=0):
+    """The k best gallery rows of a few queries, scored and selected in one pass over the gallery (csrc/search.hip): what
+    `topk_lists(cosine_scores(queries, gallery), k, cols=False)` returns, bit for bit, without the score matrix.
+    queries: fp32 [Q, D], Q <= SEARCH_MAX_QUERIES (more raises NotImplementedError: callers chunk); gallery: fp32 [N, D] holding
+    global rows row0 .. row0 + N - 1.  Tensor rules of `topk_lists`: GPU only, a row-strided view is taken as it is.
+    -> (idx int32 [Q, k] global rows, -1 where k > N; val float32 [Q, k]; (key int64 [Q, k], val)).  The last pair is a column part
+    in the layout of `topk_lists`: `topk_merge_cols` merges the parts of gallery shards into the lists of the whole gallery.
+    n_slabs pins the number of gallery slabs that select independently before the merge (0: the library's choice, else
+    1 .. SEARCH_MAX_SLABS); every value gives the same bytes."""
+    lib = _lib.load()
+    for t, nm in ((queries, "queries"), (gallery, "gallery")):
+        if not torch.is_tensor(t):
+            raise TypeError("search_topk: %s must be a torch tensor" % nm)
+        if t.dim() != 2:
+            raise ValueError("search_topk: %s must be 2-D, got shape %s" % (nm, tuple(t.shape)))
+    Q_, G_ = _dev_view(queries, torch.float32), _dev_view(gallery, torch.float32)
+    if Q_.device != G_.device:
+        raise ValueError("search_topk: queries are on %s, the gallery on %s" % (Q_.device, G_.device))
+    nq, D = Q_.shape
+    N = G_.shape[0]
+    if G_.shape[1] != D:
+        raise ValueError("search_topk: queries have %d columns, the gallery %d" % (D, G_.shape[1]))
+    k, n_slabs = int(k), int(n_slabs)
+    if nq > SEARCH_MAX_QUERIES:
+        raise NotImplementedError("search_topk: %d queries > ITR_SEARCH_MAX_QUERIES = %d per call: chunk the queries"
+                                  % (nq, SEARCH_MAX_QUERIES))
+    if k < 1 or k > TOPK_MAX:
+        raise NotImplementedError("search_topk: k = %d outside 1 .. ITR_TOPK_MAX = %d" % (k, TOPK_MAX))
+    dev = Q_.device
+    idx = torch.empty(nq, k, device=dev, dtype=torch.int32)
+    key = torch.empty(nq, k, device=dev, dtype=torch.int64)
+    val = torch.empty(nq, k, device=dev, dtype=torch.float32)
+    if nq == 0:
+        return idx, val, (key, val)
+    if D == 0:
+        raise ValueError("search_topk: D must be >= 1")
+    wsb = lib.itr_search_topk_workspace_bytes(nq, N, k, n_slabs)
+    ws = torch.empty(wsb // 8 + 1, device=dev, dtype=torch.int64)
+    _lib.check(lib.itr_search_topk(_p(Q_), Q_.stride(0), nq, _p(G_), G_.stride(0) if N else D, int(row0), N, D, k, n_slabs, _p(key), _p(val),
+                                   _p(idx), _p(ws), wsb, _stream()))
+    return idx, val, (key, val)
+
+
 # ------------------------------------------------------------------------------------------ hubness correction (csrc/hubness.hip)
 def _hub_matrix(who, S):
     """A 2-D float32 / float64 GPU matrix as the hubness kernels take it (a row-strided view is kept) -> (view, f64 flag)."""

@@ -572,6 +572,37 @@ size_t itr_topk_fold_workspace_bytes(int64_t n_rows_local, int64_t Nc, int K);
 int itr_topk_fold_cols(const float *S, int64_t ldS, int64_t row0, int64_t n_rows_local, int64_t Nc, int K,
                        uint64_t *col_key, float *col_val, void *workspace, size_t workspace_bytes, itr_stream_t stream);
 
+/* ---- query-time search: top-K of a few queries against a resident gallery (csrc/search.hip) ----
+ * The reference ranks a query by scoring it against everything, cosine_sim (Objectives.py:18-21), and sorting the line,
+ * inds = np.argsort(sims[index])[::-1] (evaluation.py:169 i2t, :209 t2i).  itr_search_topk does both for n_queries
+ * (1 .. ITR_SEARCH_MAX_QUERIES) query vectors [n_queries, D] against gallery rows [n_gallery, D] (fp32, leading dimensions
+ * ldq, ldg >= D, any alignment) in ONE pass over the gallery; the score matrix is never written.
+ *   - Score: the bits of itr_cosine_scores(queries, gallery): ONE fp32 fmaf chain per pair from +0.0, acc = fmaf(q_k, g_k, acc),
+ *     in the k order of the tile GEMM behind that entry (inside every block of 8: k = 0, 4, 1, 5, 2, 6, 3, 7; blocks ascending; D
+ *     zero-padded to a multiple of 32).  No split over D, no other order.
+ *   - Order: the ranker's key of (score, row0 + local row): larger score first, the higher index on exact ties, -0.0 == +0.0,
+ *     NaN as +inf.
+ *   - key [n_queries, K] (uint64) / val [n_queries, K] in exactly the layout of itr_topk's column part: best first, key =
+ *     ordered score << 32 | GLOBAL row, val the score's own bits, key 0 / val 0 for an empty entry (K > n_gallery).  One call
+ *     on a gallery shard is a valid part for itr_topk_merge ([n_parts][n_queries][K]) and a valid state for
+ *     itr_topk_fold_cols.  idx (may be NULL): [n_queries, K] int32 global rows, -1 where empty.
+ *   - The lists are the K largest keys of the query's n_gallery keys: a function of that set alone, independent of how the
+ *     gallery is cut into slabs, of scheduling and of how the queries are grouped inside the launch.  n_slabs pins the number of
+ *     gallery slabs that select partial lists independently before the final merge: 0 = the library's choice, else
+ *     1 .. ITR_SEARCH_MAX_SLABS; every value gives the same bytes.
+ *   - workspace: itr_search_topk_workspace_bytes(n_queries, n_gallery, K, n_slabs) bytes, 8-byte aligned, caller-owned.  No
+ *     allocation, no host read-back, no atomics on floats.
+ * Checked before any device call: null pointers, ldq / ldg < D, negative sizes, D < 1, n_slabs out of range, rows beyond the
+ * key's 32-bit index -> ITR_ERR_BADARG; K outside 1 .. ITR_TOPK_MAX or n_queries > ITR_SEARCH_MAX_QUERIES ->
+ * ITR_ERR_UNSUPPORTED; n_queries == 0 -> ITR_OK, nothing launched; n_gallery == 0 -> ITR_OK, all-empty lists written.
+ * Purely additive: no existing signature changes, ITR_ABI_VERSION stays 35. */
+#define ITR_SEARCH_MAX_QUERIES 64
+#define ITR_SEARCH_MAX_SLABS 1024
+size_t itr_search_topk_workspace_bytes(int64_t n_queries, int64_t n_gallery, int K, int n_slabs);
+int itr_search_topk(const float *queries, int64_t ldq, int64_t n_queries, const float *gallery, int64_t ldg, int64_t row0,
+                    int64_t n_gallery, int64_t D, int K, int n_slabs, uint64_t *key, float *val, int32_t *idx,
+                    void *workspace, size_t workspace_bytes, itr_stream_t stream);
+
 /* ---- hubness correction before ranking: CSLS and inverted softmax (csrc/hubness.hip) ----
  * Both corrections subtract a per-image and a per-caption vector, S'[i, j] = S[i, j] - a[i] - b[j]; a is constant along a row and
  * b along a column, so one adjusted matrix serves both directions and every consumer above works on it unchanged.  The vectors
