@@ -5,7 +5,7 @@
 // twice has two equal keys: the entry that stood earlier in the coarse list stays first, so the result is one well-defined
 // permutation.  Scores move as bit patterns.  One workgroup of 64 threads per list, one bitonic sort of <= 128 entries in LDS.
 #include "itr_internal.h"
-#include "rank_key.h"
+#include "select.h"
 
 namespace itr {
 
@@ -17,27 +17,17 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_lists_kernel(const int32_t 
     __shared__ unsigned long long key[ITR_TOPK_MAX];
     __shared__ int pos[ITR_TOPK_MAX];
     const int64_t base = (int64_t)blockIdx.x * K;
-    int L = 1;
-    while (L < K) L <<= 1;
+    const int L = next_pow2(K);
     for (int i = threadIdx.x; i < L; i += RR_THREADS) {
-        // every real key is > 0 (the smallest score key, that of -inf, is 0x007fffff): 0 marks the padding behind the list
-        key[i] = i < K ? rank_key(__uint_as_float(val[base + i]), (uint32_t)idx[base + i]) : 0ull;
+        key[i] = i < K ? rank_key(__uint_as_float(val[base + i]), (uint32_t)idx[base + i]) : KEY_EMPTY;      // the padding behind the list
         pos[i] = i;
     }
     __syncthreads();
-    for (int k = 2; k <= L; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < L; i += RR_THREADS) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const unsigned long long x = key[i], y = key[p];
-                    const int px = pos[i], py = pos[p];
-                    const bool y_first = y > x || (y == x && py < px);      // y sorts before x
-                    if ((i & k) == 0 ? y_first : !y_first) { key[i] = y; key[p] = x; pos[i] = py; pos[p] = px; }
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_desc<RR_THREADS>(L, 1, [&](int, int a, int b) {
+        const unsigned long long x = key[a], y = key[b];
+        const int px = pos[a], py = pos[b];
+        if (y > x || (y == x && py < px)) { key[a] = y; key[b] = x; pos[a] = py; pos[b] = px; }      // by key, then the lower old position
+    });
     for (int i = threadIdx.x; i < K; i += RR_THREADS) {
         const int o = pos[i];
         idx_out[base + i] = idx[base + o];

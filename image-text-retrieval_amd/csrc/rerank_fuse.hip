@@ -7,7 +7,7 @@
 // fused_out carries the computed double unchanged (a NaN stays NaN), member scores move as bit patterns.  One workgroup of 64
 // threads per list, one bitonic sort of <= 128 (key, index, position) entries in LDS; idx is a sort key only, never an address.
 #include "itr_internal.h"
-#include "rank_key.h"
+#include "select.h"
 
 namespace itr {
 
@@ -22,11 +22,9 @@ __global__ __launch_bounds__(RF_THREADS) void rerank_fuse_kernel(const int32_t *
     __shared__ double fused[ITR_TOPK_MAX];                // by OLD position
     const int64_t base = (int64_t)blockIdx.x * K;
     const int64_t plane = n * K;
-    int L = 1;
-    while (L < K) L <<= 1;
+    const int L = next_pow2(K);
     for (int i = threadIdx.x; i < L; i += RF_THREADS) {
-        // every real key is > 0 (the smallest, that of -inf, is 0x000fffffffffffff): 0 marks the padding behind the list
-        unsigned long long k = 0ull, t = 0ull;
+        unsigned long long k = KEY_EMPTY, t = 0ull;            // the padding behind the list
         if (i < K) {
             double acc = (double)__uint_as_float(val[base + i]);
             for (int m = 1; m < M; ++m) acc += (double)__uint_as_float(val[(int64_t)m * plane + base + i]);
@@ -39,19 +37,11 @@ __global__ __launch_bounds__(RF_THREADS) void rerank_fuse_kernel(const int32_t *
         tie[i] = i < K ? t : (unsigned long long)(~(uint32_t)i);
     }
     __syncthreads();
-    for (int k = 2; k <= L; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < L; i += RF_THREADS) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const unsigned long long x = key[i], y = key[p];
-                    const unsigned long long tx = tie[i], ty = tie[p];
-                    const bool y_first = y > x || (y == x && ty > tx);      // y sorts before x
-                    if ((i & k) == 0 ? y_first : !y_first) { key[i] = y; key[p] = x; tie[i] = ty; tie[p] = tx; }
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_desc<RF_THREADS>(L, 1, [&](int, int a, int b) {
+        const unsigned long long x = key[a], y = key[b];
+        const unsigned long long tx = tie[a], ty = tie[b];
+        if (y > x || (y == x && ty > tx)) { key[a] = y; key[b] = x; tie[a] = ty; tie[b] = tx; }      // by key, then the larger tie word
+    });
     for (int i = threadIdx.x; i < K; i += RF_THREADS) {
         const int o = (int)(~(uint32_t)tie[i]);             // old position, < K: the padding sorted behind every real entry
         idx_out[base + i] = (int32_t)(tie[i] >> 32);

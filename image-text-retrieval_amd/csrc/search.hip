@@ -29,7 +29,7 @@
 // search_merge_kernel then merges the slabs' parts, up to 32 at a time (one workgroup per query and group: one bitonic sort of all
 // their entries), in as many levels as it takes; the last level writes key / val / idx.  DESIGN.md 4.4.5.
 #include "itr_internal.h"
-#include "rank_key.h"
+#include "select.h"
 
 namespace itr {
 
@@ -43,28 +43,19 @@ constexpr int SR_MERGE_CAP = SR_MERGE_PARTS * ITR_TOPK_MAX;
 static_assert(ITR_SEARCH_MAX_QUERIES == 64, "the widest instance holds 16 query groups of 4");
 
 __device__ __forceinline__ int sr_min(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int sr_pow2(int n) { int L = 1; while (L < n) L <<= 1; return L; }
 
-// n_seg independent descending bitonic sorts of L (a power of two) entries, segment s at [s * L, (s + 1) * L); the scores' bits
-// move with their keys.  Ends on a barrier.
-__device__ void sr_sort_desc(unsigned long long *k, uint32_t *v, int L, int n_seg) {
-    const int total = L * n_seg;
-    for (int s = 2; s <= L; s <<= 1)
-        for (int j = s >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < total; i += SR_THREADS) {
-                const int li = i & (L - 1), p = li ^ j;
-                if (p > li) {
-                    const int a = i, b = i - li + p;
-                    const unsigned long long x = k[a], y = k[b];
-                    if ((li & s) == 0 ? y > x : x > y) {
-                        const uint32_t vx = v[a], vy = v[b];
-                        k[a] = y; k[b] = x;
-                        v[a] = vy; v[b] = vx;
-                    }
-                }
-            }
-            __syncthreads();
+// n_seg independent descending sorts (select.h's network) of L entries, segment s at [s * L, (s + 1) * L); the scores' bits move
+// with their keys
+__device__ __forceinline__ void sr_sort_desc(unsigned long long *k, uint32_t *v, int L, int n_seg) {
+    bitonic_desc<SR_THREADS>(L, n_seg, [=](int s, int a, int b) {
+        a += s * L; b += s * L;
+        const unsigned long long x = k[a], y = k[b];
+        if (y > x) {
+            const uint32_t vx = v[a], vy = v[b];
+            k[a] = y; k[b] = x;
+            v[a] = vy; v[b] = vx;
         }
+    });
 }
 
 // NQG query groups of 4.  VEC: both operands are 16-byte aligned with leading dimensions that are multiples of 4.
@@ -111,7 +102,7 @@ __global__ __launch_bounds__(SR_THREADS, 2) void search_slab_kernel(const float 
 
     const int n_rows = (int)(r_end - r_begin);            // (< 2^31: checked by the caller)
     const int n_tiles = (n_rows + TR - 1) / TR, n_ch = (D + SR_KC - 1) / SR_KC;
-    const int L = sr_pow2(K + CAND), G = SR_SORT / L;
+    const int L = next_pow2(K + CAND), G = SR_SORT / L;
 
     // chunk `c` of tile `t` -> registers.  A row past the slab reads the slab's last row (never offered); k past D reads 0 (the GEMM's padding).
     float4 gr[GU], qr[QU];
@@ -272,7 +263,7 @@ __global__ __launch_bounds__(SR_THREADS) void search_merge_kernel(const unsigned
     __shared__ unsigned long long sk[SR_MERGE_CAP];
     __shared__ uint32_t sv[SR_MERGE_CAP];
     const int tid = threadIdx.x, q = blockIdx.y, p0 = blockIdx.x * SR_MERGE_PARTS, np = sr_min(SR_MERGE_PARTS, P - p0);
-    const int n = np > 0 ? np * K : 0, L = sr_pow2(n > K ? n : K);
+    const int n = np > 0 ? np * K : 0, L = next_pow2(n > K ? n : K);
     for (int e = tid; e < L; e += SR_THREADS) {
         unsigned long long key = 0ull;
         uint32_t val = 0u;
@@ -289,7 +280,7 @@ __global__ __launch_bounds__(SR_THREADS) void search_merge_kernel(const unsigned
         const unsigned long long key = sk[i];
         key_out[o + i] = key;
         val_out[o + i] = sv[i];                           // (an empty entry carries score bits 0)
-        if (FINAL && idx_out) idx_out[o + i] = key != 0ull ? (int32_t)(uint32_t)key : -1;
+        if (FINAL && idx_out) idx_out[o + i] = key_index(key);
     }
 }
 
@@ -310,13 +301,15 @@ static SearchPlan search_plan(int64_t n_queries, int64_t n_gallery, int K, int n
     return p;
 }
 
-// parts of the slabs, then of every merge level but the last
-struct SearchWs { unsigned long long *key[3]; uint32_t *val[3]; size_t bytes; };
+// The merge levels: parts[0] parts of the slabs, then what every merge level but the last leaves.  The walk that sizes the workspace
+// is the one itr_search_topk's launches follow; all zero (no parts, null pointers) is an empty gallery.
+struct SearchWs { int64_t parts[3]; unsigned long long *key[3]; uint32_t *val[3]; size_t bytes; };
 static SearchWs search_ws(void *base, int64_t n_queries, int64_t n_gallery, int K, int n_slabs) {
     WsCarver c(base);
     SearchWs w{};
     int64_t parts = search_plan(n_queries, n_gallery, K, n_slabs).slabs;
     for (int lvl = 0; lvl < 3; ++lvl) {
+        w.parts[lvl] = parts;
         w.key[lvl] = c.take<unsigned long long>((size_t)(parts * n_queries * K) * 8);
         w.val[lvl] = c.take<uint32_t>((size_t)(parts * n_queries * K) * 4);
         if (parts <= SR_MERGE_PARTS) break;
@@ -325,6 +318,7 @@ static SearchWs search_ws(void *base, int64_t n_queries, int64_t n_gallery, int 
     w.bytes = c.bytes;
     return w;
 }
+static_assert(ITR_SEARCH_MAX_SLABS <= SR_MERGE_PARTS * SR_MERGE_PARTS * SR_MERGE_PARTS, "three levels bring every slab count down to one group");
 
 template <int NQG>
 static void slab_launch(bool vec, unsigned slabs, hipStream_t st, const float *Q, int64_t ldq, int nq, const float *G, int64_t ldg, int64_t row0,
@@ -359,38 +353,27 @@ extern "C" int itr_search_topk(const float *queries, int64_t ldq, int64_t n_quer
     const int nq = (int)n_queries;
     unsigned long long *kout = reinterpret_cast<unsigned long long *>(key);
     uint32_t *vout = reinterpret_cast<uint32_t *>(val);
-    if (n_gallery == 0) {                                  // no parts: the last merge level writes empty lists
-        hipLaunchKernelGGL(itr::search_merge_kernel<true>, dim3(1, nq), dim3(itr::SR_THREADS), 0, st, (const unsigned long long *)nullptr,
-                           (const uint32_t *)nullptr, 0, nq, K, kout, vout, idx);
-        ITR_CHECK_LAUNCH("search_merge");
-        return ITR_OK;
+    itr::SearchWs ws{};                                    // an empty gallery: no parts, the last merge level writes empty lists
+    if (n_gallery > 0) {
+        const size_t need = itr_search_topk_workspace_bytes(n_queries, n_gallery, K, n_slabs);
+        ITR_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+                    "itr_search_topk: workspace missing, misaligned or smaller than itr_search_topk_workspace_bytes");
+        const itr::SearchPlan p = itr::search_plan(n_queries, n_gallery, K, n_slabs);
+        ws = itr::search_ws(workspace, n_queries, n_gallery, K, n_slabs);
+        const bool vec = ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(gallery)) & 15) == 0 && ldq % 4 == 0 && ldg % 4 == 0;
+        if (p.nqg == 1) itr::slab_launch<1>(vec, (unsigned)p.slabs, st, queries, ldq, nq, gallery, ldg, row0, n_gallery, (int)D, K, p.rows_per_slab, ws.key[0], ws.val[0]);
+        else if (p.nqg == 4) itr::slab_launch<4>(vec, (unsigned)p.slabs, st, queries, ldq, nq, gallery, ldg, row0, n_gallery, (int)D, K, p.rows_per_slab, ws.key[0], ws.val[0]);
+        else itr::slab_launch<16>(vec, (unsigned)p.slabs, st, queries, ldq, nq, gallery, ldg, row0, n_gallery, (int)D, K, p.rows_per_slab, ws.key[0], ws.val[0]);
+        ITR_CHECK_LAUNCH("search_slab");
     }
-    const size_t need = itr_search_topk_workspace_bytes(n_queries, n_gallery, K, n_slabs);
-    ITR_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
-                "itr_search_topk: workspace missing, misaligned or smaller than itr_search_topk_workspace_bytes");
-    const itr::SearchPlan p = itr::search_plan(n_queries, n_gallery, K, n_slabs);
-    const itr::SearchWs ws = itr::search_ws(workspace, n_queries, n_gallery, K, n_slabs);
-    const bool vec = ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(gallery)) & 15) == 0 && ldq % 4 == 0 && ldg % 4 == 0;
-    if (p.nqg == 1) itr::slab_launch<1>(vec, (unsigned)p.slabs, st, queries, ldq, nq, gallery, ldg, row0, n_gallery, (int)D, K, p.rows_per_slab, ws.key[0], ws.val[0]);
-    else if (p.nqg == 4) itr::slab_launch<4>(vec, (unsigned)p.slabs, st, queries, ldq, nq, gallery, ldg, row0, n_gallery, (int)D, K, p.rows_per_slab, ws.key[0], ws.val[0]);
-    else itr::slab_launch<16>(vec, (unsigned)p.slabs, st, queries, ldq, nq, gallery, ldg, row0, n_gallery, (int)D, K, p.rows_per_slab, ws.key[0], ws.val[0]);
-    ITR_CHECK_LAUNCH("search_slab");
-    int64_t parts = p.slabs;
-    for (int lvl = 0; parts > itr::SR_MERGE_PARTS; ++lvl) {
-        const int64_t groups = itr::ceil_div(parts, (int64_t)itr::SR_MERGE_PARTS);
-        hipLaunchKernelGGL(itr::search_merge_kernel<false>, dim3((unsigned)groups, nq), dim3(itr::SR_THREADS), 0, st, ws.key[lvl], ws.val[lvl],
-                           (int)parts, nq, K, ws.key[lvl + 1], ws.val[lvl + 1], (int32_t *)nullptr);
+    int lvl = 0;
+    for (; ws.parts[lvl] > itr::SR_MERGE_PARTS; ++lvl) {
+        hipLaunchKernelGGL(itr::search_merge_kernel<false>, dim3((unsigned)ws.parts[lvl + 1], nq), dim3(itr::SR_THREADS), 0, st, ws.key[lvl],
+                           ws.val[lvl], (int)ws.parts[lvl], nq, K, ws.key[lvl + 1], ws.val[lvl + 1], (int32_t *)nullptr);
         ITR_CHECK_LAUNCH("search_merge");
-        parts = groups;
-        if (parts <= itr::SR_MERGE_PARTS) {
-            hipLaunchKernelGGL(itr::search_merge_kernel<true>, dim3(1, nq), dim3(itr::SR_THREADS), 0, st, ws.key[lvl + 1], ws.val[lvl + 1],
-                               (int)parts, nq, K, kout, vout, idx);
-            ITR_CHECK_LAUNCH("search_merge");
-            return ITR_OK;
-        }
     }
-    hipLaunchKernelGGL(itr::search_merge_kernel<true>, dim3(1, nq), dim3(itr::SR_THREADS), 0, st, ws.key[0], ws.val[0], (int)parts, nq, K, kout,
-                       vout, idx);
+    hipLaunchKernelGGL(itr::search_merge_kernel<true>, dim3(1, nq), dim3(itr::SR_THREADS), 0, st, ws.key[lvl], ws.val[lvl], (int)ws.parts[lvl], nq,
+                       K, kout, vout, idx);
     ITR_CHECK_LAUNCH("search_merge");
     return ITR_OK;
 }

@@ -16,7 +16,7 @@
 // Two passes over S (one per direction), not one: a fused pass would have to keep K-lists for every column of a tile next to the
 // rows' state (K up to 128: 1 KB per column), which does not fit LDS at a useful tile width.  DESIGN.md 4.5.
 #include "itr_internal.h"
-#include "rank_key.h"
+#include "select.h"
 
 namespace itr {
 
@@ -32,10 +32,8 @@ static_assert(TK_ROW_CAP - ITR_TOPK_MAX >= TK_THREADS * 4, "a row's candidate sp
 struct Key96 { unsigned long long s; uint32_t i; uint32_t pad; };
 __device__ __forceinline__ bool key_gt(unsigned long long a, unsigned long long b) { return a > b; }
 __device__ __forceinline__ bool key_gt(const Key96 &a, const Key96 &b) { return a.s > b.s || (a.s == b.s && a.i > b.i); }
-__device__ __forceinline__ uint32_t key_idx(unsigned long long k) { return (uint32_t)k; }
+// select.h's entry convention for the 96-bit key: empty when its score key is 0
 __device__ __forceinline__ uint32_t key_idx(const Key96 &k) { return k.i; }
-// every real key is > 0 (the smallest score key, that of -inf, is 0x007fffff / 0x000fffffffffffff): 0 marks an empty entry
-__device__ __forceinline__ bool key_set(unsigned long long k) { return k != 0; }
 __device__ __forceinline__ bool key_set(const Key96 &k) { return k.s != 0; }
 
 template <typename T> struct TopkTraits;
@@ -50,24 +48,14 @@ template <> struct TopkTraits<double> {
     static __device__ __forceinline__ Key zero() { Key96 k; k.s = 0; k.i = 0; k.pad = 0; return k; }
 };
 
-__device__ __forceinline__ int next_pow2(int n) { int L = 1; while (L < n) L <<= 1; return L; }
-
-// n_seg independent descending bitonic sorts of L (a power of two) entries each, segment q at buf + q * stride.  Ends on a barrier.
+// n_seg independent descending sorts (select.h's network, ordered by key_gt) of L keys each, segment q at buf + q * stride
 template <typename Key>
-__device__ void sort_desc(Key *buf, int L, int stride, int n_seg) {
-    const int total = L * n_seg;
-    for (int k = 2; k <= L; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < total; i += blockDim.x) {
-                const int li = i & (L - 1), p = li ^ j;
-                if (p > li) {
-                    Key *b = buf + (i / L) * stride;
-                    const Key x = b[li], y = b[p];
-                    if ((li & k) == 0 ? key_gt(y, x) : key_gt(x, y)) { b[li] = y; b[p] = x; }
-                }
-            }
-            __syncthreads();
-        }
+__device__ __forceinline__ void sort_desc(Key *buf, int L, int stride, int n_seg) {
+    bitonic_desc<TK_THREADS>(L, n_seg, [=](int q, int a, int b) {
+        Key *s = buf + q * stride;
+        const Key x = s[a], y = s[b];
+        if (key_gt(y, x)) { s[a] = y; s[b] = x; }
+    });
 }
 
 // ---- i2t: one workgroup per row -------------------------------------------------------------------------------------------------
@@ -251,7 +239,7 @@ __global__ __launch_bounds__(TK_MERGE_THREADS) void topk_merge_kernel(const unsi
         }
         const int64_t w = j * K + o;
         if (key_out) key_out[w] = best;
-        if (idx_out) idx_out[w] = bp >= 0 ? (int32_t)(uint32_t)best : -1;
+        if (idx_out) idx_out[w] = key_index(best);
         val_out[w] = v;
     }
 }

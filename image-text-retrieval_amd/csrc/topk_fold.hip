@@ -24,7 +24,7 @@
 //      written; the one that lands on K - 1 is the column's new threshold.
 // No serial chain over K, no workspace, nothing order-dependent.  DESIGN.md 4.4.2.
 #include "itr_internal.h"
-#include "rank_key.h"
+#include "select.h"
 
 namespace itr {
 
@@ -91,30 +91,20 @@ __global__ __launch_bounds__(TF_THREADS, 4) void topk_fold_kernel(const float *_
         int mx = 0;
         for (int q = 0; q < TF_COLS; ++q) mx = s_cnt[q] > mx ? s_cnt[q] : mx;
         if (mx == 0) return;                               // (uniform)
-        mx = tf_min(mx, TF_CAND);
-        int L = 1;
-        while (L < mx) L <<= 1;
-        const int total_c = TF_COLS * L;
+        const int L = next_pow2(tf_min(mx, TF_CAND)), total_c = TF_COLS * L;
         for (int i = tid; i < total_c; i += TF_THREADS) {
             const int q = i / L, li = i % L;
             if (li >= tf_min(s_cnt[q], TF_CAND)) { ck[q][li] = 0ull; cv[q][li] = 0u; }
         }
         __syncthreads();
-        for (int k = 2; k <= L; k <<= 1)                   // TF_COLS descending bitonic sorts of L entries, scores carried
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < total_c; i += TF_THREADS) {
-                    const int q = i / L, li = i & (L - 1), p = li ^ j;
-                    if (p > li) {
-                        const unsigned long long x = ck[q][li], y = ck[q][p];
-                        if ((li & k) == 0 ? y > x : x > y) {
-                            const uint32_t vx = cv[q][li], vy = cv[q][p];
-                            ck[q][li] = y; ck[q][p] = x;
-                            cv[q][li] = vy; cv[q][p] = vx;
-                        }
-                    }
-                }
-                __syncthreads();
+        bitonic_desc<TF_THREADS>(L, TF_COLS, [&](int q, int a, int b) {      // TF_COLS descending sorts of L entries, scores carried
+            const unsigned long long x = ck[q][a], y = ck[q][b];
+            if (y > x) {
+                const uint32_t vx = cv[q][a], vy = cv[q][b];
+                ck[q][a] = y; ck[q][b] = x;
+                cv[q][a] = vy; cv[q][b] = vx;
             }
+        });
         // where every candidate lands: its index among its column's candidates + #{old entries above it} (binary search in the old
         // list, where it lies; empty entries, key 0, are below every key).  The whole strip at once: ONE chain of dependent loads.
         for (int i = tid; i < total_c; i += TF_THREADS) {

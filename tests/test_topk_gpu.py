@@ -166,6 +166,41 @@ def test_topk_full_size(dev, k):
     assert (_bits(rv.cpu().numpy()) == _bits(wrv)).all() and (_bits(cv.cpu().numpy()) == _bits(wcv)).all()
 
 
+def test_topk_family_agrees_at_power_of_two_seams(dev):
+    """K = L and K = L +- 1 of the shared sorting network (csrc/select.h): the row, slab, column and fold kernels and the two
+    re-sorts give one list per query, equal to the numpy order in indices and score bits."""
+    rng = np.random.RandomState(11)
+    q = rng.randn(5, 36).astype(np.float32)
+    g = rng.randn(300, 36).astype(np.float32)
+    g[10:20] = g[3]                                              # exact score ties
+    queries, gallery = torch.from_numpy(q).to(dev), torch.from_numpy(g).to(dev)
+    # the same values as column slices of 37-wide buffers: rows not 16-byte aligned, leading dimension % 4 != 0
+    q_odd = torch.zeros(5, 37, device=dev)[:, 1:].copy_(queries)
+    g_odd = torch.zeros(300, 37, device=dev)[:, 1:].copy_(gallery)
+    assert g_odd.data_ptr() % 16 != 0 and g_odd.stride(0) == 37
+    S = ops.cosine_scores(queries, gallery)
+    S_host = S.cpu().numpy()
+    St = S.t().contiguous()
+    for k in (1, 2, 63, 64, 65, 127, 128):
+        wi, wv = T.topk_rows(S_host, k)
+        ri, rv, _ = ops.topk_lists(S, k, cols=False)
+        got = {"rows": (ri, rv)}
+        for n_slabs in (0, 1, 3):
+            got["search %d" % n_slabs] = ops.search_topk(queries, gallery, k, n_slabs=n_slabs)[:2]
+            got["search %d, unaligned" % n_slabs] = ops.search_topk(q_odd, g_odd, k, n_slabs=n_slabs)[:2]
+        got["cols"] = ops.topk_merge_cols([ops.topk_lists(St, k, rows=False)[2]], k)
+        lo_hi = ops.topk_fold_cols(St[170:], k, row0=170, state=ops.topk_fold_cols(St[:170], k, row0=0))
+        hi_lo = ops.topk_fold_cols(St[:170], k, row0=0, state=ops.topk_fold_cols(St[170:], k, row0=170))
+        got["fold"], got["fold, reversed"] = ops.topk_merge_cols([lo_hi], k), ops.topk_merge_cols([hi_lo], k)
+        got["rerank"] = ops.rerank_lists(ri.flip(1).contiguous(), rv.flip(1).contiguous())[:2]
+        fi, fused, fv, _ = ops.rerank_fused_lists(ri.flip(1).contiguous(), [rv.flip(1).contiguous()])
+        got["rerank_fused"] = (fi, fv[0])
+        assert (fused.cpu().numpy() == wv.astype(np.float64)).all(), k
+        for name, (i, v) in got.items():
+            assert i.shape == (5, k) and (i.cpu().numpy() == wi).all(), (name, k)
+            assert (_bits(v.cpu().numpy()) == _bits(wv)).all(), (name, k)
+
+
 # ---- end to end: evalrank_single / _ensemble / _fast with topk
 def _toy_checkpoints(golden, tmp_path, seeds=(1, 2)):
     from test_evalrank_gpu import _materialise, _scan_cfg

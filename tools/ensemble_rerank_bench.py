@@ -31,7 +31,7 @@ def run_arms(arms, rounds):
     for _ in range(rounds):                                      # interleaved rounds: every arm once per round
         for k in arms:
             times[k].append(timed(arms[k]))
-    return {k: (float(np.median(v)), float(np.min(v))) for k, v in times.items()}
+    return {k: (float(np.median(v)), float(np.min(v)), [round(float(np.percentile(v, p)), 4) for p in (25, 75)]) for k, v in times.items()}
 
 
 def main():
@@ -53,8 +53,8 @@ def main():
     v0 = vals[0].contiguous()
     res = run_arms({"rerank_lists": lambda: ops.rerank_lists(idx, v0), "rerank_fused_lists M=2": lambda: ops.rerank_fused_lists(idx, vals)},
                    a.rounds)
-    for k, (med, mn) in res.items():
-        print(json.dumps({"part": "a", "arm": k, "lists": n, "K": K, "ms_median": round(med, 4), "ms_min": round(mn, 4),
+    for k, (med, mn, quart) in res.items():
+        print(json.dumps({"part": "a", "arm": k, "lists": n, "K": K, "ms_median": round(med, 4), "ms_min": round(mn, 4), "ms_p25_p75": quart,
                           "over_rerank_lists": round(med / res["rerank_lists"][0], 2), "device": name}), flush=True)
     del idx, vals, v0
 
@@ -107,8 +107,8 @@ def main():
     res = run_arms(arms, a.rounds)
     scoring = res["dense scoring (2 x sgraf_scores)"][0]
     full = res["dense ensemble (scoring + f64 average + rank_counts_f64)"][0]
-    for k, (med, mn) in res.items():
-        print(json.dumps({"part": "b", "arm": k, "images": Ni, "captions": Nc, "ms_median": round(med, 3), "ms_min": round(mn, 3),
+    for k, (med, mn, quart) in res.items():
+        print(json.dumps({"part": "b", "arm": k, "images": Ni, "captions": Nc, "ms_median": round(med, 3), "ms_min": round(mn, 3), "ms_p25_p75": quart,
                           "dense_scoring_over_arm": round(scoring / med, 2), "dense_ensemble_over_arm": round(full / med, 2),
                           "device": name}), flush=True)
     # the fused list scores are the dense average's at the listed pairs (fp32 member scores from two kernels: not bit-equal)

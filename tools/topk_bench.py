@@ -74,6 +74,7 @@ def main():
     for name, (_, b) in cases.items():
         med = float(np.median(times[name]))
         out[name] = round(med, 1)
+        out[name + "_p25_p75"] = [round(float(np.percentile(times[name], p)), 1) for p in (25, 75)]
         out[name + "_TBps"] = round(b / (med * 1e-6) / 1e12, 2)
         out[name + "_frac_8TBps"] = round(b / (med * 1e-6) / HBM, 3)
     out["faster_than_torch_pair"] = {k: out["topk_both_k%d" % k] < out["torch_topk_pair_k%d" % k] for k in (1, 10, 100)}
